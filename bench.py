@@ -8,10 +8,12 @@ Workload at N=1: BASELINE.json configs[1] -- batch 12, 192x640 KITTI-shaped trip
 
   python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run, one rank per GPU)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step and the run's details).  A plain run sets up,
+warms up, times the K steps and prints the line; --dump-outputs DIR also writes what the last timed step computed as DIR/<name>.npy
+(write_outputs).  --full adds two objects, each from work of its own after the timed region (never part of `value`):
   roofline     conv stage (igemm + wgrad MFMA kernels): algorithmic FLOPs / summed kernel time, measured with HIP events
-               on the launch stream in a separate instrumented step after the timed region (never part of `value`)
-  cpu_baseline the CPU oracle (oracle/, stock PyTorch ops) timed on this box's host cores on a bounded sample
+               on the launch stream in separate instrumented steps (--layer-report: their per-launch table)
+  cpu_baseline the CPU oracle (oracle/, stock PyTorch ops) timed on the host cores on a bounded sample
 """
 import argparse
 import json
@@ -131,6 +133,7 @@ def make_step(depth, pose, opt, crit, samples, pair=True, graph=False):
     from mcav import nn as N
     from mcav.streams import Branch
     pose_branch = Branch()
+    outputs = {}          # network outputs of the latest step, detached (no autograd state kept alive); graphed: the captured ones, which replays rewrite
 
     def fwd_bwd(tgt, ref0, ref1, K):          # the sequence of Trainer.process_batch (unsupervised-pseuso-lidar_amd/trainer.py)
         opt.zero_grad()
@@ -138,6 +141,7 @@ def make_step(depth, pose, opt, crit, samples, pair=True, graph=False):
         poses = pose_branch.fork(pose, tgt, [ref0, ref1])                  # independent of the depth net until the loss: second stream
         disps = list(depth.forward_pair(tgt, ref0)) if pair else [depth(tgt), depth(ref0)]
         poses = pose_branch.join(poses)
+        outputs.update(disp_tgt=disps[0][0].detach(), disp_ref0=disps[1][0].detach(), poses=poses.detach())
         loss = crit.forward(tgt, [ref0, ref1], disps, poses, K, None)
         sum(loss).backward()
         return tuple(loss)
@@ -166,7 +170,25 @@ def make_step(depth, pose, opt, crit, samples, pair=True, graph=False):
         opt.grad_scale = mdist.allreduce_gradients(opt.arena()) if collective else 1.0 / mdist.world()
         opt.step()
         return loss
+    step.outputs = outputs
     return step
+
+
+DUMP_MAX_ELEMENTS = 1 << 21       # per array (8 MB as float32): the five arrays of write_outputs stay under 64 MB
+
+
+def write_outputs(path, outputs, loss, arena):
+    """What a caller of the timed step receives from its last call, as <path>/<name>.npy in float32: the loss terms, the finest disparity
+    of both depth passes, the poses, and the parameters and gradients it left in the arena.  An array above DUMP_MAX_ELEMENTS elements is
+    written as a fixed, seeded sample of its flattened elements (the same positions in every run of the same arguments)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(outputs, loss=torch.stack([l.detach().reshape(()) for l in loss]), params=arena.flat, grads=arena.gflat)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(H, W, depth_layers=18, ssim=False, batch=4, warm=1, steps=5):
@@ -224,8 +246,13 @@ def main():
     ap.set_defaults(graph=False)
     ap.add_argument("--serial", action="store_true", help="issue the whole step on ONE stream (for rocprofv3 kernel statistics whose per-kernel "
                                                           "durations are free of cross-stream overlap; slower than the default three streams)")
-    ap.add_argument("--layer-report", default=None, help="write a per-launch table of the instrumented step to this file")
+    ap.add_argument("--layer-report", default=None, help="write a per-launch table of the instrumented step to this file (needs --full)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure the roofline (instrumented steps) and the CPU oracle "
+                                                        "baseline; a plain run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.layer_report and not args.full:
+        ap.error("--layer-report is a table of the roofline's instrumented steps: add --full")
     if os.environ.get("MCAV_BENCH_WATCHDOG"):          # debugging aid: dump every thread's stack and exit if the run exceeds N seconds
         import faulthandler
         faulthandler.dump_traceback_later(int(os.environ["MCAV_BENCH_WATCHDOG"]), exit=True)
@@ -324,7 +351,10 @@ def main():
                                "parameters_equal_across_ranks": agree["parameters_equal_across_ranks"],
                                "parameter_checksum": agree["parameter_checksum"], "loss_per_rank": agree.get("loss_per_rank")}
 
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, step.outputs, loss, opt.arena())
+
+    if rank == 0 and args.full and not args.no_roofline:
         # instrumented step(s): every conv kernel dispatched with its own start/stop HIP events (csrc/kernel_timer.h), on one stream
         from mcav import streams
         serial_before, streams.SERIAL = streams.SERIAL, True      # one stream: no other kernel runs beside the one being timed
@@ -451,7 +481,7 @@ def main():
                                     "kernel": "%s (one launch: per-sample constants, warp + loss forward/backward, finalize), 52 B/pixel x %d pixels" % ("warp_loss_ssim_kernel" if args.ssim else "warp_loss_l1_kernel", B * H * W),
                                     "ms": round(lms, 4), "main_kernel_ms": round(lmain, 4),
                                     "note": "achieved = 52 B/pixel over the loss stage's one launch (per-dispatch HIP events); traffic = PMC bytes of the kernel"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         # SURVEY.md 8d asks for 3 warm-up + 10 timed steps: taken when the run itself is the full-length one (--steps >= 100, the default)
         full = args.steps >= 100
         out["cpu_baseline"] = cpu_baseline(H, W, args.depth_layers, args.ssim, warm=3 if full else 1, steps=10 if full else 5)

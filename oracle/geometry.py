@@ -92,6 +92,34 @@ def reconstruct(depth, K):
     return rays * depth.unsqueeze(1)
 
 
+def _k_chain(A, X):
+    acc = A[:, :, 0:1] * X[:, 0:1, :]
+    for k in range(1, A.shape[2]):
+        acc = (A[:, :, k:k + 1].double() * X[:, k:k + 1, :].double() + acc.double()).float()
+    return acc
+
+
+class _KChainMatmul(torch.autograd.Function):
+    """fp32 A [B,M,K] @ X [B,K,N] (K small) with every entry as the chain fma(a_K-1, x_K-1, ... fma(a_1, x_1, a_0 x_0)) -- what the AVX-512
+    sgemm kernel that computed the reference's golden vectors forms, in the product and in its data gradient A^T @ G -- so that the oracle
+    does not depend on which BLAS kernel this host picks (another kernel's rounding moves the ill-conditioned inverse warp's disparity
+    gradient by 1e-5 .. 1e-4).  A float64 product plus a float64 sum, rounded once to fp32, is that fma."""
+
+    @staticmethod
+    def forward(ctx, A, X):
+        ctx.save_for_backward(A, X)
+        return _k_chain(A, X)
+
+    @staticmethod
+    def backward(ctx, G):
+        A, X = ctx.saved_tensors
+        return G @ X.transpose(1, 2), _k_chain(A.transpose(1, 2), G)
+
+
+def _matmul_k_chain(A, X):
+    return _KChainMatmul.apply(A, X) if A.dtype == torch.float32 else A @ X
+
+
 def project(X, K, Tcw):
     """X [B,3,H,W], K [B,3,3], Tcw [B,4,4] -> sampling grid [B,H,W,2] in [-1,1] (x, y)."""
     B, _, H, W = X.shape
@@ -99,7 +127,7 @@ def project(X, K, Tcw):
     K4 = torch.eye(4, dtype=X.dtype, device=K.device).repeat(B, 1, 1)      # float32 for float32 points, as the reference's torch.eye(4)
     K4[:, :3, :3] = K
     P = (K4 @ Tcw)[:, :3, :]
-    cam = P @ Xh
+    cam = _matmul_k_chain(P, Xh)
     pix = cam[:, :2, :] / (cam[:, 2:3, :] + 1e-5)
     pix = pix.view(B, 2, H, W).permute(0, 2, 3, 1)
     gx = pix[..., 0] / (W - 1)

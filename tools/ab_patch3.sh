@@ -12,5 +12,5 @@ d = json.loads(sys.stdin.read())
 print('patch3=$v rep=$rep: %.3f ms  %.1f /s' % (d['ms_per_step'], d['value']))" >> $OUT/ab_patch3.txt
   done
 done
-MCAV_PATCH3=1 python3 $ROOT/bench.py --no-cpu-baseline --steps 20 --warmup 5 --layer-report $OUT/p3_layers.txt > /dev/null 2>&1
+MCAV_PATCH3=1 python3 $ROOT/bench.py --full --no-cpu-baseline --steps 20 --warmup 5 --layer-report $OUT/p3_layers.txt > /dev/null 2>&1
 cat $OUT/ab_patch3.txt

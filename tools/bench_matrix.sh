@@ -4,7 +4,7 @@
 TAG=${1:-r}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
-run() { name=$1; shift; python3 $ROOT/bench.py "$@" > $OUT/${TAG}_bench_$name.json 2> $OUT/${TAG}_bench_$name.err; echo "$name: $(cut -c1-160 $OUT/${TAG}_bench_$name.json)"; }
+run() { name=$1; shift; python3 $ROOT/bench.py --full "$@" > $OUT/${TAG}_bench_$name.json 2> $OUT/${TAG}_bench_$name.err; echo "$name: $(cut -c1-160 $OUT/${TAG}_bench_$name.json)"; }
 run default --layer-report $OUT/${TAG}_layers.txt
 run fp32_mfma --dtype fp32-mfma --no-cpu-baseline --steps 50 --warmup 10 --layer-report $OUT/${TAG}_layers_fp32_mfma.txt
 run default_graph --graph --no-cpu-baseline --steps 50 --warmup 10
