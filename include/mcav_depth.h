@@ -46,6 +46,11 @@ int mcav_abi_version(void);
 #define MCAV_WL_NO_SMOOTH 4u      /* leave the smoothness term out (used for scales > 0 of multi-scale nets) */
 #define MCAV_WL_INPUT_DEPTH 8u    /* disp_t / disp_r0 already hold depths; gradients are w.r.t. depth */
 #define MCAV_WL_SSIM 16u          /* photometric term = 0.85 * SSIM distance + 0.15 * L1 (reference losses.py:12-54, weights of :77) instead of L1 */
+/* masked modes, mcav_warp_loss_masked_fwd_bwd only (the monodepth2 recipe, without its random noise on the identity error).  e_w(p): warp w's
+ * per-pixel error (channel mean of the photometric term), i_w(p): the same error of its UNWARPED source against its target. */
+#define MCAV_WL_MIN_REPROJ 32u    /* warps 0 and 1 (same target) become one term, mean_p min(e_0, e_1), of weight tw[0] + tw[1]; warp 2 unchanged */
+#define MCAV_WL_AUTOMASK 64u      /* every term takes the minimum with its warps' identity errors: min(i_0, i_1, e_0, e_1) with MIN_REPROJ,
+                                     else min(i_w, e_w) per warp.  A pixel won by an identity error adds it to the loss and has no gradient */
 
 /* The workspace holds per-workgroup partial sums and the completion tickets of the fused kernel (since round 3 the per-sample constants and
  * the float64 finalize run INSIDE it: one launch).  It must be ZERO-FILLED before its first use; every launch leaves the tickets at zero, so
@@ -63,6 +68,22 @@ int mcav_warp_loss_fwd_bwd(const float* tgt, const float* ref0, const float* ref
                            int B, int H, int W, unsigned flags, const float* upstream, const float* term_weights,
                            float* losses, float* d_disp_t, float* d_disp_r0, float* d_poses,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* mcav_warp_loss_fwd_bwd with the masked modes: the same arguments and outputs, flags may add MCAV_WL_MIN_REPROJ / MCAV_WL_AUTOMASK.
+ * Ties are deterministic: identity wins over reprojection on equality (a warp is kept only if e < i); among the identity errors and among
+ * the reprojection errors warp 0 wins.  Only the selected reprojection receives gradient; a re-run on the same inputs selects the same.
+ * selection: optional uint8 [B,2,H,W] on the DEVICE (NULL = not written; selection_bytes >= B*2*H*W):
+ *   plane 0: the group of warps 0 and 1: 0 = warp 0, 1 = warp 1, 2 = identity.  Without MIN_REPROJ it holds warp 0's choice (0 = kept,
+ *            2 = identity); warp 1's choice is not stored;
+ *   plane 1: warp 2: 0 = kept, 2 = identity.
+ * With neither new flag this is mcav_warp_loss_fwd_bwd (bit-identical results; the selection, if given, is zero-filled).
+ * Returns MCAV_E_INVALID for unknown flag bits, MCAV_E_WORKSPACE for a selection buffer that is too small. */
+int mcav_warp_loss_masked_fwd_bwd(const float* tgt, const float* ref0, const float* ref1,
+                                  const float* disp_t, const float* disp_r0, const float* poses, const void* K,
+                                  int B, int H, int W, unsigned flags, const float* upstream, const float* term_weights,
+                                  float* losses, float* d_disp_t, float* d_disp_r0, float* d_poses,
+                                  void* workspace, size_t workspace_bytes, void* stream,
+                                  unsigned char* selection, size_t selection_bytes);
 
 /* DIAGNOSTIC twin of mcav_warp_loss_fwd_bwd (upstream (1,1)): the same kernel bodies with a per-pixel dump, used by
  * tests/flip_finder.py to NAME the pixels at which an fp32 evaluation takes another bilinear cell / L1 sign than float64 does

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times the fused loss stage alone (forward call = forward + backward of the loss in ONE launch) at bench.py's shapes.
-usage: python tools/loss_bench.py [--ssim] [--batch 12 --height 192 --width 640] [--iters 200]"""
+usage: python tools/loss_bench.py [--ssim] [--min-reprojection] [--automask] [--batch 12 --height 192 --width 640] [--iters 200]"""
 import argparse
 import os
 import sys
@@ -13,6 +13,8 @@ from oracle.step import synthetic_batch  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--ssim", action="store_true")
+ap.add_argument("--min-reprojection", action="store_true")
+ap.add_argument("--automask", action="store_true")
 ap.add_argument("--batch", type=int, default=12)
 ap.add_argument("--height", type=int, default=192)
 ap.add_argument("--width", type=int, default=640)
@@ -35,7 +37,7 @@ def smooth_disp():
 
 dt, dr = smooth_disp(), smooth_disp()
 poses = (0.01 * torch.randn(B, 2, 6, generator=g)).to(dev)
-crit = Losses(ssim=a.ssim)
+crit = Losses(ssim=a.ssim, min_reprojection=a.min_reprojection, automask=a.automask)
 from mcav import nn as N  # noqa: E402
 
 with torch.no_grad():
@@ -57,5 +59,6 @@ with torch.no_grad():
     durs = sorted(N.kernel_timer_end())
 us = 1000.0 * durs[len(durs) // 2]
 print("loss stage %s %dx%dx%d: kernel %.1f us (median of %d dispatches, min %.1f) = %.3f of the 8 TB/s HBM roofline at 52 B/pixel; %.1f us per "
-      "back-to-back call incl. the host; losses %s" % ("SSIM+L1" if a.ssim else "L1", B, H, W, us, len(durs), 1000.0 * durs[0],
+      "back-to-back call incl. the host; losses %s" % (("SSIM+L1" if a.ssim else "L1") + (" min-reprojection" if a.min_reprojection else "") +
+                                                       (" automask" if a.automask else ""), B, H, W, us, len(durs), 1000.0 * durs[0],
                                                        52.0 * B * H * W / (us * 1e-6) / 8e12, call_us, [round(float(x), 6) for x in out]))

@@ -367,6 +367,38 @@ MCAV_HD void warp_unit_fast(const float (*q)[4], const float* tv, const FTap& t,
     dD += backproject_fast(t, X, gix, giy, H, W, dP);
 }
 
+// warp_unit_fast without its backward: sum of |residual| and the UNWEIGHTED sums of sign(res) * d sample / d (ix, iy).  The masked modes
+// (MCAV_WL_MIN_REPROJ / MCAV_WL_AUTOMASK) know which warp a pixel's gradient belongs to only after every candidate's error is known.
+MCAV_HD void warp_eval_fast(const float (*q)[4], const float* tv, const FTap& t, float& labs, float& gix, float& giy) {
+    labs = 0.f; gix = 0.f; giy = 0.f;
+    for (int c = 0; c < 3; ++c) {
+        const Sample s = bilinear_lerp(q[c][0], q[c][1], q[c][2], q[c][3], t.wx1, t.wy1);
+        const float res = s.v - tv[c];
+        labs += fabsf(res);
+        const float sg = sgn_exact(res);
+        gix = fmaf(sg, s.dvdx, gix);
+        giy = fmaf(sg, s.dvdy, giy);
+    }
+}
+
+// backproject_fast in two steps, for a derivative held until its weight is known: the unweighted d / d c (3 floats) and d / d D of a tap ...
+MCAV_HD float backproject_dc(const FTap& t, float gix, float giy, int H, int W, float* dc) {
+    const float w1 = (float)(W - 1), h1 = (float)(H - 1);
+    const float dpx = (gix * (w1 * 0.5f)) * (2.0f / w1), dpy = (giy * (h1 * 0.5f)) * (2.0f / h1);
+    dc[0] = dpx * t.zi;
+    dc[1] = dpy * t.zi;
+    dc[2] = -(fmaf(dpx, t.px, dpy * t.py)) * t.zi;
+    return fmaf(dc[0], t.q0, fmaf(dc[1], t.q1, dc[2] * t.q2));
+}
+// ... and the 12 dP sums with the weight k (the caller adds k * the returned d / d D)
+MCAV_HD void apply_dc(const float* dc, float k, const float* X, float* dP) {
+    for (int i = 0; i < 3; ++i) {
+        const float d = k * dc[i];
+        dP[4 * i + 0] = fmaf(d, X[0], dP[4 * i + 0]); dP[4 * i + 1] = fmaf(d, X[1], dP[4 * i + 1]); dP[4 * i + 2] = fmaf(d, X[2], dP[4 * i + 2]);
+        dP[4 * i + 3] += d;
+    }
+}
+
 // the four texels of a tap straight from a plane (standalone / SSIM kernels, host check)
 MCAV_HD void texels_of(const float* plane, int W, const FTap& t, float* q4) {
     q4[0] = t.in00 ? plane[t.y0 * W + t.x0] : 0.0f;

@@ -18,7 +18,7 @@ from mcav import lib as L
 
 class _WarpLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, disp_t, disp_r, poses, tgt, ref0, ref1, K, flags, term_weights):
+    def forward(ctx, disp_t, disp_r, poses, tgt, ref0, ref1, K, flags, term_weights, selection=None):
         B, _, H, W = tgt.shape
         for n, t in (("tgt", tgt), ("ref0", ref0), ("ref1", ref1), ("disp_t", disp_t), ("disp_r", disp_r), ("poses", poses)):
             L.dev(t, n)
@@ -36,7 +36,12 @@ class _WarpLossFn(torch.autograd.Function):
         tail = [tw, L.ptr(losses), L.ptr(g_dt), L.ptr(g_dr), L.ptr(g_p), L.ptr(ws), ws.numel(), L.stream()]
         from mcav import nn as N
         i0 = h.mcav_kernel_timer_count() if N.PROFILE_LOSS is not None else 0
-        L.check(h.mcav_warp_loss_fwd_bwd(*args, flags, None, *tail), "mcav_warp_loss_fwd_bwd")
+        masked = (flags & (L.WL_MIN_REPROJ | L.WL_AUTOMASK)) != 0
+        if masked:          # min-reprojection / auto-masking: the same kernels' masked instantiations (include/mcav_depth.h)
+            sel = [L.ptr(selection), selection.numel() if selection is not None else 0]
+            L.check(h.mcav_warp_loss_masked_fwd_bwd(*args, flags, None, *tail, *sel), "mcav_warp_loss_masked_fwd_bwd")
+        else:
+            L.check(h.mcav_warp_loss_fwd_bwd(*args, flags, None, *tail), "mcav_warp_loss_fwd_bwd")
         if N.PROFILE_LOSS is not None:
             N.PROFILE_LOSS.append(("warp_loss", i0, h.mcav_kernel_timer_count()))       # ONE launch since round 3 (prepare / finalize folded in)
         ctx.rerun = (args, tail, flags, (tgt, ref0, ref1, disp_t, disp_r, poses, K, ws, losses))
@@ -61,8 +66,12 @@ class _WarpLossFn(torch.autograd.Function):
         tail = list(tail)
         tail[1] = L.ptr(scratch)        # loss values are not needed again
         # no-op on the device when upstream == (1, 1); otherwise recomputes the gradients with the real weights
-        L.check(L.lib().mcav_warp_loss_fwd_bwd(*args, flags | L.WL_SKIP_IF_UNIT, L.ptr(up), *tail), "mcav_warp_loss_fwd_bwd(bwd)")
-        return g_dt, g_dr, g_p, None, None, None, None, None, None
+        if flags & (L.WL_MIN_REPROJ | L.WL_AUTOMASK):      # (the re-run selects exactly as the first run did: same inputs, same code)
+            L.check(L.lib().mcav_warp_loss_masked_fwd_bwd(*args, flags | L.WL_SKIP_IF_UNIT, L.ptr(up), *tail, L.ptr(None), 0),
+                    "mcav_warp_loss_masked_fwd_bwd(bwd)")
+        else:
+            L.check(L.lib().mcav_warp_loss_fwd_bwd(*args, flags | L.WL_SKIP_IF_UNIT, L.ptr(up), *tail), "mcav_warp_loss_fwd_bwd(bwd)")
+        return g_dt, g_dr, g_p, None, None, None, None, None, None, None
 
 
 class SSIM:
@@ -83,26 +92,57 @@ class Losses:
     """`Losses()` is the reference's live loss (L1 photometric, losses.py:183-240).  `Losses(ssim=True)` -- or setting `.ssim` on an
     instance, which is what `loss: {ssim: true}` in a trainer config does -- switches the photometric term of every warp to
     0.85 * SSIM.standard_loss(warped, target) + 0.15 * |target - warped| (the mix of the reference's dormant
-    compute_photometric_loss, losses.py:66-77, without its mean + 0.5 std clip), evaluated by the same fused kernel (MCAV_WL_SSIM)."""
+    compute_photometric_loss, losses.py:66-77, without its mean + 0.5 std clip), evaluated by the same fused kernel (MCAV_WL_SSIM).
 
-    def __init__(self, ssim=False):
+    `min_reprojection` / `automask` (attributes as well; trainer config `loss: {min_reprojection: true, automask: true}`) combine the
+    pixels of the photometric term as monodepth2 does, in the same fused kernel (MCAV_WL_MIN_REPROJ / MCAV_WL_AUTOMASK,
+    include/mcav_depth.h): the two warps into the target view become one term, the per-pixel minimum of their errors; auto-masking takes
+    the minimum with the identity (unwarped) errors as well, and a pixel an identity error wins sends no gradient.  Ties are deterministic
+    (identity first, then warp 0).  With `keep_selection` the last forward's selection maps stay in `.selection`, one uint8 [B,2,H,W]
+    tensor per scale (plane 0: warps 0 / 1 -> 0 / 1, identity 2; plane 1: warp 2 kept 0, identity 2)."""
+
+    def __init__(self, ssim=False, min_reprojection=False, automask=False, keep_selection=False):
         self.clip_loss = 0.5
         self.ssim = bool(ssim)
+        self.min_reprojection = bool(min_reprojection)
+        self.automask = bool(automask)
+        self.keep_selection = bool(keep_selection)
+        self.selection = None
 
     def _flags(self, n_scales):
         return L.WL_SSIM if self.ssim else 0
+
+    def _mask_flags(self):
+        return (L.WL_MIN_REPROJ if self.min_reprojection else 0) | (L.WL_AUTOMASK if self.automask else 0)
+
+    def _selection(self, tgt):
+        if not self.keep_selection:
+            return None
+        B, _, H, W = tgt.shape
+        alloc = torch.empty if self._mask_flags() else torch.zeros      # (the plain loss keeps every warp: all zeros)
+        return alloc((B, 2, H, W), dtype=torch.uint8, device=tgt.device)
 
     def forward(self, tgt_img, ref_imgs, disparity, poses, intrinsics, gt=None):
         """-> [loss_mam, loss_smooth].  disparity = [disps(tgt), disps(ref0)], each a list over scales."""
         disp_t, disp_r = disparity[0], disparity[1]
         n = len(disp_t)
         ssim_flag = self._flags(max(n, len(disp_r)))
+        mask_flags = self._mask_flags()
         if n != 1 or len(disp_r) != 1:
             from mcav.multiscale import multiscale_losses
-            return multiscale_losses(tgt_img, ref_imgs, disparity, poses, intrinsics, ssim=self.ssim)
+            sel = [] if self.keep_selection else None
+            out = multiscale_losses(tgt_img, ref_imgs, disparity, poses, intrinsics, ssim=self.ssim, min_reprojection=self.min_reprojection,
+                                    automask=self.automask, selections=sel)
+            if sel is not None:
+                self.selection = sel
+            return out
         tw = (0.25, 0.25, 0.5)     # mean of the two tgt-view L1 terms and the third term, averaged (losses.py:227-240)
+        sel = self._selection(tgt_img)
         l0, l1 = _WarpLossFn.apply(disp_t[0].contiguous(), disp_r[0].contiguous(), poses.contiguous(), tgt_img.contiguous(),
-                                   ref_imgs[0].contiguous(), ref_imgs[1].contiguous(), intrinsics.contiguous(), ssim_flag, tw)
+                                   ref_imgs[0].contiguous(), ref_imgs[1].contiguous(), intrinsics.contiguous(), ssim_flag | mask_flags, tw,
+                                   sel)
+        if sel is not None:
+            self.selection = [sel]
         return [l0, l1]
 
     def reprojection_loss(self, tgt, refs, depths, poses, intrinsics, mode='min'):

@@ -15,6 +15,7 @@ c_f = ctypes.c_float
 c_sz = ctypes.c_size_t
 
 WL_K_F64, WL_SKIP_IF_UNIT, WL_NO_SMOOTH, WL_INPUT_DEPTH, WL_SSIM = 1, 2, 4, 8, 16
+WL_MIN_REPROJ, WL_AUTOMASK = 32, 64      # mcav_warp_loss_masked_fwd_bwd only
 
 
 class MCAVError(RuntimeError):
@@ -27,6 +28,7 @@ _SIGNATURES = {
     "mcav_abi_version": (c_i, []),
     "mcav_warp_loss_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "mcav_warp_loss_fwd_bwd": (c_i, [c_p] * 7 + [c_i, c_i, c_i, c_u, c_p, c_p] + [c_p] * 4 + [c_p, c_sz, c_p]),
+    "mcav_warp_loss_masked_fwd_bwd": (c_i, [c_p] * 7 + [c_i, c_i, c_i, c_u, c_p, c_p] + [c_p] * 4 + [c_p, c_sz, c_p, c_p, c_sz]),
     "mcav_warp_loss_debug_taps": (c_i, [c_p] * 7 + [c_i, c_i, c_i, c_u, c_p] + [c_p] * 4 + [c_p, c_sz, c_p, c_sz, c_p]),
     "mcav_inverse_warp_fwd": (c_i, [c_p] * 4 + [c_i, c_i, c_i, c_i, c_u, c_p, c_p, c_sz, c_p]),
     "mcav_inverse_warp_bwd": (c_i, [c_p] * 5 + [c_i, c_i, c_i, c_i, c_u, c_p, c_p, c_p, c_sz, c_p]),

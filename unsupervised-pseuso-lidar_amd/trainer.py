@@ -74,6 +74,8 @@ class Trainer:
 
         self.criterion = Losses()
         self.criterion.ssim = bool((config.get('loss') or {}).get('ssim', False))     # opt-in SSIM + L1 photometric mix (losses.py)
+        self.criterion.min_reprojection = bool((config.get('loss') or {}).get('min_reprojection', False))   # opt-in per-pixel minimum
+        self.criterion.automask = bool((config.get('loss') or {}).get('automask', False))                   # and identity auto-masking
         from mcav.streams import Branch
         self.pose_branch = Branch()
         self.loss = None
