@@ -133,6 +133,29 @@ int mcav_smooth_loss_fwd_bwd(const float* depth, int B, int H, int W, float weig
                              float* loss_accum, float* d_depth, int accumulate,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* Edge-aware smoothness on mean-normalised disparity for ONE scale: monodepth2's get_smooth_loss(disp / (mean_disp + 1e-7), color)
+ * (layers.py get_smooth_loss, trainer.py compute_losses), the smoothness term that goes with MCAV_WL_MIN_REPROJ / MCAV_WL_AUTOMASK.
+ * disp: [B,1,h,w] sigmoid disparity of the target (NOT depth); img: [B,3,H,W] the target image as passed to the loss.
+ * f = H / h must be an integer equal to W / w; I_s = the f x f box average of img (f = 1: img itself).  Per sample b:
+ *   m_b = mean of d_b over its h*w pixels,  n = d_b / (m_b + 1e-7)
+ *   wx(y,x) = exp(-(1/3) sum_c |I_s(c,y,x) - I_s(c,y,x+1)|)  (x < w-1),   wy(y,x) likewise along y  (y < h-1)
+ *   E = 1/(B h (w-1)) sum_{b,y,x} |n(y,x) - n(y,x+1)| wx  +  1/(B (h-1) w) sum_{b,y,x} |n(y,x) - n(y+1,x)| wy
+ * A direction without pairs (w == 1 or h == 1) contributes 0.  With R_b = the weighted sum of |d_p - d_q| of sample b (the two factors
+ * included): E = sum_b R_b / (m_b + 1e-7) and dE/dd_i = dR_b/dd_i / (m_b + 1e-7) - R_b / ((m_b + 1e-7)^2 h w); |.|' at 0 is 0.
+ *
+ * mcav_edge_smooth_fwd: loss_accum[0] += weight * E (one float on the device; the same += contract as mcav_smooth_loss_fwd_bwd) and
+ *   saved[0..B) = m_b, saved[B..2B) = R_b (2B doubles on the device, read by the backward).  Two launch-internal reductions, deterministic
+ *   (float64, fixed order).  The workspace holds tickets that every launch leaves at zero: zero-fill it when it is allocated.
+ * mcav_edge_smooth_bwd: d_disp (+)= upstream[0] * weight * dE/dd from the forward's saved sums; upstream: one float on the DEVICE (NULL
+ *   means 1); accumulate != 0 adds into d_disp.  Needs no workspace.
+ * Both return MCAV_E_INVALID for a null pointer, a non-positive size, H % h, W % w, H / h != W / w or B > 4095 (ticket capacity), and
+ * the forward MCAV_E_WORKSPACE for a workspace below mcav_edge_smooth_workspace_bytes(B, h, w).  Nothing is launched then. */
+size_t mcav_edge_smooth_workspace_bytes(int B, int h, int w);
+int mcav_edge_smooth_fwd(const float* disp, const float* img, int B, int H, int W, int h, int w, float weight, double* saved,
+                         float* loss_accum, void* workspace, size_t workspace_bytes, void* stream);
+int mcav_edge_smooth_bwd(const float* disp, const float* img, int B, int H, int W, int h, int w, float weight, const double* saved,
+                         const float* upstream, float* d_disp, int accumulate, void* stream);
+
 /* ---- after the training step ------------------------------------------------------------------ */
 
 /* Depth metrics, reference evaluate.py:6-39 (compute_errors): one pass over the ground-truth depth and the network's sigmoid

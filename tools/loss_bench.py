@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Times the fused loss stage alone (forward call = forward + backward of the loss in ONE launch) at bench.py's shapes.
-usage: python tools/loss_bench.py [--ssim] [--min-reprojection] [--automask] [--batch 12 --height 192 --width 640] [--iters 200]"""
+usage: python tools/loss_bench.py [--ssim] [--min-reprojection] [--automask] [--edge-smooth] [--batch 12 --height 192 --width 640] [--iters 200]
+--edge-smooth: Losses(edge_aware_smoothness=True) -- the fused kernel runs with MCAV_WL_NO_SMOOTH, and the edge-aware smoothness launches
+(mcav_edge_smooth_fwd / _bwd, scale 0) are timed per dispatch as well."""
 import argparse
 import os
 import sys
@@ -15,6 +17,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--ssim", action="store_true")
 ap.add_argument("--min-reprojection", action="store_true")
 ap.add_argument("--automask", action="store_true")
+ap.add_argument("--edge-smooth", action="store_true")
 ap.add_argument("--batch", type=int, default=12)
 ap.add_argument("--height", type=int, default=192)
 ap.add_argument("--width", type=int, default=640)
@@ -37,7 +40,7 @@ def smooth_disp():
 
 dt, dr = smooth_disp(), smooth_disp()
 poses = (0.01 * torch.randn(B, 2, 6, generator=g)).to(dev)
-crit = Losses(ssim=a.ssim, min_reprojection=a.min_reprojection, automask=a.automask)
+crit = Losses(ssim=a.ssim, min_reprojection=a.min_reprojection, automask=a.automask, edge_aware_smoothness=a.edge_smooth)
 from mcav import nn as N  # noqa: E402
 
 with torch.no_grad():
@@ -56,9 +59,29 @@ with torch.no_grad():
     for _ in range(50):
         out = crit.forward(tgt, refs, [[dt], [dr]], poses, K, None)
     torch.cuda.synchronize()
-    durs = sorted(N.kernel_timer_end())
+    durs = N.kernel_timer_end()
+    if a.edge_smooth:                   # a call is [fused kernel, edge-aware smoothness forward]
+        durs = durs[0::2]
+    durs = sorted(durs)
 us = 1000.0 * durs[len(durs) // 2]
 print("loss stage %s %dx%dx%d: kernel %.1f us (median of %d dispatches, min %.1f) = %.3f of the 8 TB/s HBM roofline at 52 B/pixel; %.1f us per "
       "back-to-back call incl. the host; losses %s" % (("SSIM+L1" if a.ssim else "L1") + (" min-reprojection" if a.min_reprojection else "") +
                                                        (" automask" if a.automask else ""), B, H, W, us, len(durs), 1000.0 * durs[0],
                                                        52.0 * B * H * W / (us * 1e-6) / 8e12, call_us, [round(float(x), 6) for x in out]))
+if a.edge_smooth:
+    # the edge-aware smoothness alone: forward + backward of scale 0, one dispatch each (only the mcav launches are timed)
+    x = dt.clone().requires_grad_()
+    for _ in range(10):
+        crit.edge_aware_smooth_loss(x, tgt).backward()
+    torch.cuda.synchronize()
+    N.kernel_timer_begin()
+    for _ in range(50):
+        crit.edge_aware_smooth_loss(x, tgt).backward()
+    torch.cuda.synchronize()
+    d = N.kernel_timer_end()
+    assert len(d) == 100, len(d)
+    fwd, bwd = sorted(d[0::2]), sorted(d[1::2])
+    fu, bu = 1000.0 * fwd[len(fwd) // 2], 1000.0 * bwd[len(bwd) // 2]
+    print("edge-aware smoothness %dx%dx%d: forward %.1f us (min %.1f), backward %.1f us (min %.1f), %.1f us per step; fused kernel %.1f us "
+          "(median of 50 dispatches each; 16 B/pixel read forward, 20 B/pixel backward)" % (B, H, W, fu, 1000.0 * fwd[0], bu, 1000.0 * bwd[0],
+                                                                                           fu + bu, us))

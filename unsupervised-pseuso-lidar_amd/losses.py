@@ -99,15 +99,23 @@ class Losses:
     include/mcav_depth.h): the two warps into the target view become one term, the per-pixel minimum of their errors; auto-masking takes
     the minimum with the identity (unwarped) errors as well, and a pixel an identity error wins sends no gradient.  Ties are deterministic
     (identity first, then warp 0).  With `keep_selection` the last forward's selection maps stay in `.selection`, one uint8 [B,2,H,W]
-    tensor per scale (plane 0: warps 0 / 1 -> 0 / 1, identity 2; plane 1: warp 2 kept 0, identity 2)."""
+    tensor per scale (plane 0: warps 0 / 1 -> 0 / 1, identity 2; plane 1: warp 2 kept 0, identity 2).
 
-    def __init__(self, ssim=False, min_reprojection=False, automask=False, keep_selection=False):
+    `edge_aware_smoothness` (attribute as well; trainer config `loss: {edge_aware_smoothness: true, edge_smoothness_weight: 1e-3}`) replaces
+    the reference's second-order depth smoothness with monodepth2's term, `edge_aware_smooth_loss(disparities of tgt, tgt)`: first order, on
+    disparity divided by its per-image mean, weighted down at image edges, `edge_smoothness_weight` (1e-3) / n_scales * 2^-s per scale
+    (include/mcav_depth.h: mcav_edge_smooth_fwd).  loss_mam is what the same call gives without it."""
+
+    def __init__(self, ssim=False, min_reprojection=False, automask=False, keep_selection=False, edge_aware_smoothness=False,
+                 edge_smoothness_weight=1e-3):
         self.clip_loss = 0.5
         self.ssim = bool(ssim)
         self.min_reprojection = bool(min_reprojection)
         self.automask = bool(automask)
         self.keep_selection = bool(keep_selection)
         self.selection = None
+        self.edge_aware_smoothness = bool(edge_aware_smoothness)
+        self.edge_smoothness_weight = float(edge_smoothness_weight)
 
     def _flags(self, n_scales):
         return L.WL_SSIM if self.ssim else 0
@@ -132,18 +140,30 @@ class Losses:
             from mcav.multiscale import multiscale_losses
             sel = [] if self.keep_selection else None
             out = multiscale_losses(tgt_img, ref_imgs, disparity, poses, intrinsics, ssim=self.ssim, min_reprojection=self.min_reprojection,
-                                    automask=self.automask, selections=sel)
+                                    automask=self.automask, selections=sel, edge_aware_smoothness=self.edge_aware_smoothness,
+                                    edge_smoothness_weight=self.edge_smoothness_weight)
             if sel is not None:
                 self.selection = sel
             return out
         tw = (0.25, 0.25, 0.5)     # mean of the two tgt-view L1 terms and the third term, averaged (losses.py:227-240)
         sel = self._selection(tgt_img)
+        smooth_flag = L.WL_NO_SMOOTH if self.edge_aware_smoothness else 0
         l0, l1 = _WarpLossFn.apply(disp_t[0].contiguous(), disp_r[0].contiguous(), poses.contiguous(), tgt_img.contiguous(),
-                                   ref_imgs[0].contiguous(), ref_imgs[1].contiguous(), intrinsics.contiguous(), ssim_flag | mask_flags, tw,
-                                   sel)
+                                   ref_imgs[0].contiguous(), ref_imgs[1].contiguous(), intrinsics.contiguous(),
+                                   ssim_flag | mask_flags | smooth_flag, tw, sel)
         if sel is not None:
             self.selection = [sel]
+        if self.edge_aware_smoothness:
+            # l1 is exactly 0 under MCAV_WL_NO_SMOOTH; keeping it in the sum hands the fused kernel the usual upstream (1, 1) under
+            # sum(loss).backward(), so its backward stays a no-op instead of a re-run with (1, 0)
+            return [l0, l1 + self.edge_aware_smooth_loss(disp_t[0], tgt_img)]
         return [l0, l1]
+
+    def edge_aware_smooth_loss(self, disp, img):
+        """monodepth2's edge-aware smoothness of tgt's disparity (one [B,1,h,w] map or a list over scales) against the target image img
+        [B,3,H,W] (H / h = W / w an integer; coarser scales see img box-averaged to their size): edge_smoothness_weight / n * sum_s 2^-s E_s."""
+        from mcav.multiscale import edge_smooth_loss
+        return edge_smooth_loss(disp, img, self.edge_smoothness_weight)
 
     def reprojection_loss(self, tgt, refs, depths, poses, intrinsics, mode='min'):
         """Reference signature (losses.py:183): takes DEPTHS (nested [time][scale])."""

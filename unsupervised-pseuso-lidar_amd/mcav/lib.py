@@ -39,6 +39,9 @@ _SIGNATURES = {
     "mcav_ssim_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p]),
     "mcav_smooth_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "mcav_smooth_loss_fwd_bwd": (c_i, [c_p, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),
+    "mcav_edge_smooth_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
+    "mcav_edge_smooth_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_sz, c_p]),
+    "mcav_edge_smooth_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_p]),
 }
 
 

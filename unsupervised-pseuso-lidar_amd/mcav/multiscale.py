@@ -1,6 +1,7 @@
 """Loss-stage pieces that are not the fused single-scale kernel: standalone smoothness, multi-scale nets.
 
 smooth_loss: Losses.smooth_loss (reference losses.py:242-260) for a list of depth scales, weight /2.3 per scale.
+edge_smooth_loss: monodepth2's edge-aware smoothness on mean-normalised disparity (Losses(edge_aware_smoothness=True)).
 multiscale_losses: Losses.forward for depth nets that return several scales (DispNetS): every coarser depth is
 bilinearly resized to full resolution before warping (losses.py:212-216); smoothness stays at native resolution.
 """
@@ -54,6 +55,60 @@ def smooth_loss(pred_map):
     return _SmoothFn.apply(*[m.contiguous() for m in pred_map])
 
 
+class _EdgeSmoothFn(torch.autograd.Function):
+    """monodepth2's edge-aware smoothness on mean-normalised disparity (include/mcav_depth.h: mcav_edge_smooth_fwd / _bwd), summed over
+    scales with the given weights.  Forward: one launch per scale into one accumulator; the per-sample sums each launch saves feed its
+    backward, which reads autograd's upstream from the device (no host sync: capturable)."""
+
+    @staticmethod
+    def forward(ctx, img, weights, *maps):
+        h = L.lib()
+        L.dev(img, "image")
+        B, C, H, W = img.shape
+        if C != 3:
+            raise L.MCAVError("edge-aware smoothness expects a [B,3,H,W] image")
+        dev = img.device
+        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        saved = []
+        for D, wt in zip(maps, weights):
+            L.dev(D, "disparity")
+            if D.dim() != 4 or D.shape[0] != B or D.shape[1] != 1:
+                raise L.MCAVError("edge-aware smoothness expects [B,1,h,w] disparities of the image's batch")
+            hh, ww = D.shape[-2:]
+            ws = L.workspace(max(h.mcav_edge_smooth_workspace_bytes(B, hh, ww), 1), dev, "edge_smooth", zero=True)
+            sv = torch.empty(2 * B, dtype=torch.float64, device=dev)
+            L.check(h.mcav_edge_smooth_fwd(L.ptr(D), L.ptr(img), B, H, W, hh, ww, wt, L.ptr(sv), L.ptr(loss), L.ptr(ws), ws.numel(),
+                                           L.stream()), "mcav_edge_smooth_fwd")
+            saved.append(sv)
+        ctx.keep = (img, maps, weights, saved)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        h = L.lib()
+        img, maps, weights, saved = ctx.keep
+        B, _, H, W = img.shape
+        up = g.reshape(1).to(torch.float32).contiguous()
+        grads = []
+        for D, wt, sv in zip(maps, weights, saved):
+            hh, ww = D.shape[-2:]
+            gD = torch.empty_like(D)
+            L.check(h.mcav_edge_smooth_bwd(L.ptr(D), L.ptr(img), B, H, W, hh, ww, wt, L.ptr(sv), L.ptr(up), L.ptr(gD), 0, L.stream()),
+                    "mcav_edge_smooth_bwd")
+            grads.append(gD)
+        return (None, None, *grads)
+
+
+def edge_smooth_loss(disp, img, weight=1e-3):
+    """Edge-aware smoothness of one disparity map or a list over scales (monodepth2): weight / n * sum_s 2^-s E_s(disp_s, img box-averaged
+    to scale s's size).  disp: sigmoid disparities [B,1,h,w] (not depths); img: the target image [B,3,H,W], H / h = W / w an integer."""
+    if not isinstance(disp, (tuple, list)):
+        disp = [disp]
+    n = len(disp)
+    weights = tuple(float(weight) / n * 2.0 ** -s for s in range(n))
+    return _EdgeSmoothFn.apply(img.contiguous(), weights, *[d.contiguous() for d in disp])
+
+
 class _ResizeFn(torch.autograd.Function):
     """F.interpolate(D, [H, W], mode='bilinear', align_corners=False) on [B,1,h,w] maps (losses.py:214-215)."""
 
@@ -76,12 +131,13 @@ class _ResizeFn(torch.autograd.Function):
 
 
 def multiscale_losses(tgt, refs, disparity, poses, K, inputs_are_depth=False, ssim=False, min_reprojection=False, automask=False,
-                      selections=None):
+                      selections=None, edge_aware_smoothness=False, edge_smoothness_weight=1e-3):
     """Losses.forward for depth nets that return several scales (DispNetS).  Per scale: depth (from disparity), bilinear resize
     to the image size, the fused 3-warp kernel (L1, or the 0.85 SSIM + 0.15 L1 mix when ssim: the reference composes its photometric
     term per scale, losses.py:209-221) on the resized depths; smoothness on the native-resolution depths of tgt.
     min_reprojection / automask: the masked modes of losses.Losses, applied per scale; selections: a list that receives each scale's
-    selection map (uint8 [B,2,H,W])."""
+    selection map (uint8 [B,2,H,W]).  edge_aware_smoothness: the smoothness term is edge_smooth_loss(disparities of tgt, tgt,
+    edge_smoothness_weight) instead (disparity inputs only)."""
     import losses as LS                      # the fused kernel's autograd node
     from geometry.pose_geometry import disp_to_depth
     from mcav import tape  # noqa: F401  (registers the resize entry points)
@@ -104,4 +160,8 @@ def multiscale_losses(tgt, refs, disparity, poses, K, inputs_are_depth=False, ss
         l0, _ = LS._WarpLossFn.apply(Dt.contiguous(), Dr.contiguous(), poses.contiguous(), tgt.contiguous(), refs[0].contiguous(),
                                      refs[1].contiguous(), K.contiguous(), flags, tw, sel)
         total = l0 if total is None else total + l0
+    if edge_aware_smoothness:
+        if inputs_are_depth:
+            raise L.MCAVError("edge-aware smoothness acts on disparities, not depths")
+        return [total, edge_smooth_loss(disparity[0], tgt, edge_smoothness_weight)]
     return [total, smooth_loss(depths[0])]

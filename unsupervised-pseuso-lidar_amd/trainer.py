@@ -76,6 +76,8 @@ class Trainer:
         self.criterion.ssim = bool((config.get('loss') or {}).get('ssim', False))     # opt-in SSIM + L1 photometric mix (losses.py)
         self.criterion.min_reprojection = bool((config.get('loss') or {}).get('min_reprojection', False))   # opt-in per-pixel minimum
         self.criterion.automask = bool((config.get('loss') or {}).get('automask', False))                   # and identity auto-masking
+        self.criterion.edge_aware_smoothness = bool((config.get('loss') or {}).get('edge_aware_smoothness', False))   # monodepth2's smoothness
+        self.criterion.edge_smoothness_weight = float((config.get('loss') or {}).get('edge_smoothness_weight', 1e-3))
         from mcav.streams import Branch
         self.pose_branch = Branch()
         self.loss = None
