@@ -167,6 +167,32 @@ size_t mcav_depth_metrics_workspace_bytes(void);
 int mcav_depth_metrics(const float* gt, const float* disp, size_t n, float min_gt, float* out10, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* The KITTI depth evaluation protocol (monodepth2 evaluate_depth.py, monodepth evaluation_utils.py), per image, at the ground truth's own
+ * resolution.  The definition is tests/eval_protocol_ref.py; for image b with true size (Hb, Wb) = sizes[b] and crop box boxes[b]:
+ *   up   = disp[b] (h x w) resized to Hb x Wb, bilinear with half-pixel centres and edge clamping (F.interpolate, align_corners=False)
+ *   pred = 1 / (10 up + 0.01) * scale                 float32, each operation rounded (numpy float32)
+ *   mask = min_depth < gt < max_depth, inside the half-open box [y0, y1) x [x0, x1)
+ *   with MCAV_EVAL_MEDIAN_SCALING: ratio = median(gt[mask]) / median(pred[mask]) (exact medians as np.median on float32), pred *= ratio
+ *   pred = clip(pred, min_depth, max_depth), metrics over the mask as mcav_depth_metrics (sq_rel the squared-relative error).
+ * gt: device [B,Hg,Wg] metres (0 = no return), padded: only [0, Hb) x [0, Wb) of each image is read, the padding may hold anything.
+ * disp: device [B,h,w] sigmoid disparity.  sizes: device int [B,2] (Hb, Wb); boxes: device int [B,4] (y0, y1, x0, x1); both clamped in the
+ * kernels (Hb to [0, Hg], the box to the true size), so no value reads out of bounds.
+ * rows: device [B,11] = { silog, abs_rel, log10, rms, sq_rel, log_rms, d1, d2, d3, count, ratio } per image (ratio 1 without scaling).
+ *   An image without a masked pixel gets count 0 and NaN everywhere else; a NaN prediction inside the mask makes its metrics NaN.
+ * Deterministic: no float atomics, float64 sums in a fixed order; rows are bit-identical from run to run.  No host synchronisation,
+ * allocation or copy: the call can be captured in a hipGraph.  10 launches with scaling, 2 without.
+ * Workspace (mcav_eval_depth_workspace_bytes, each piece rounded up to 256 bytes):
+ *   B * 8  +  B * 32  +  B * 32768  +  B * 8 * Hg * Wg  +  B * 88 * ceil(Hg * Wg / 2048)   bytes
+ *   (counters, selection state, 2048-bin histograms, the masked gt / pred keys, the per-workgroup float64 sums).  No zero-fill needed.
+ * Returns MCAV_E_INVALID for a null pointer, a non-positive size, unknown flag bits, min_depth <= 0, max_depth <= min_depth or a
+ * non-finite scale, MCAV_E_WORKSPACE for a workspace below mcav_eval_depth_workspace_bytes(B, Hg, Wg); nothing is launched then. */
+#define MCAV_EVAL_MEDIAN_SCALING 1
+size_t mcav_eval_depth_workspace_bytes(int B, int Hg, int Wg);
+int mcav_eval_depth(const float* gt, const float* disp, int B, int Hg, int Wg, int h, int w,
+                    const int* sizes, const int* boxes,
+                    float min_depth, float max_depth, float scale, int flags,
+                    float* rows, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Depth image -> pseudo-LiDAR cloud, reference pseudo-lidar/utils/PseudoLiDAR.py:69-110 (project_PL) with :39-46
  * (inverse_rigid_trans): un-project with P_rect_02, transform into the velodyne frame, keep x >= 0 and z < 1 m, keep every
  * sparsity-th survivor (0 = all), in pixel order; float64 like the reference's numpy arithmetic; 4th column 0 as in the reference.

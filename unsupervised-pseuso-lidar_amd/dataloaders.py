@@ -6,6 +6,8 @@ tree, KITTI itself is not available offline), the transform chain on the GPU (Gp
 the one-batch-ahead PrefetchLoader that joins them.  Not built: the OXTS pose packets of the semi-supervised experiment.  What the
 training step consumes is kept: a dict with 'tgt' [3,H,W], 'ref_imgs' [2 x [3,H,W]], 'intrinsics' [3,3] fp64,
 'groundtruth' [1,H,W] (reference dataloaders.py:226-251).  SyntheticTriplets produces such samples from a seed.
+`datasets.groundtruth: native` (opt-in, for evaluate.evaluate_depth): the ground truth stays at its own size, in metres, and PrefetchLoader
+zero-pads each batch to its largest map and adds 'groundtruth_size' [B,2] int32 (host).  The loss never reads the ground truth.
 """
 import ctypes
 
@@ -171,6 +173,10 @@ class KittiDataset(Dataset):
         self.img_width = ds['augmentation']['image_width']
         self.img_height = ds['augmentation']['image_height']
         self.seq_len = ds.get('sequence_length', 3)
+        gt_mode = ds.get('groundtruth', 'resized')
+        if gt_mode not in ('resized', 'native'):
+            raise ValueError("datasets.groundtruth must be 'resized' (default) or 'native', got %r" % (gt_mode,))
+        self.native_gt = gt_mode == 'native'      # the ground truth unresized, in metres (the KITTI evaluation protocol)
         self.transforms = transforms
         self.raw = transforms is None
         self.samples = []
@@ -200,11 +206,14 @@ class KittiDataset(Dataset):
 
     def load_img(self, path, gt=False):
         """-> (image, original height, original width).  raw mode: uint8 [H0, W0, 3] tensor (the GPU runs the chain); ground truth: the
-        depth PNG as float32, resized with Pillow's bilinear filter on mode 'F' (what ToPILImage + Resize do to a float map), [1, h, w]."""
+        depth PNG as float32, resized with Pillow's bilinear filter on mode 'F' (what ToPILImage + Resize do to a float map), [1, h, w];
+        with datasets.groundtruth: native, the PNG / 256 (metres) at its own size, [1, H0, W0] float32."""
         from PIL import Image
         img = Image.open(self.resolve(path))
         if gt:
             arr = np.asarray(img, dtype=np.float32)
+            if self.native_gt and self.transforms is None:
+                return torch.from_numpy(arr / np.float32(256.0))[None], arr.shape[0], arr.shape[1]
             if self.transforms is not None:
                 for t in self.transforms[:-1]:
                     arr = t(arr)
@@ -231,6 +240,8 @@ class KittiDataset(Dataset):
         ret['intrinsics'] = torch.from_numpy(K)
         if sample.get('groundtruth'):
             ret['groundtruth'] = self.load_img(sample['groundtruth'], gt=True)[0]
+        elif self.native_gt and self.raw:
+            ret['groundtruth'] = torch.zeros(1, og_h, og_w)      # no map: no valid pixel (evaluate_depth leaves the image out)
         else:
             ret['groundtruth'] = torch.zeros(1, self.img_height, self.img_width)
         return ret
@@ -262,13 +273,16 @@ class PrefetchLoader:
     """One batch ahead: a background thread takes the DataLoader's raw sample lists, copies the decoded uint8 frames to the GPU through pinned
     memory on its own stream, runs the fused /255 + Pillow-exact resize + Normalize kernel there (GpuImageTransform, grouped by source size)
     and hands the trainer finished batches in the reference's collated layout (tgt [B,3,h,w], ref_imgs 2 x [B,3,h,w], intrinsics [B,3,3] fp64,
-    groundtruth [B,1,h,w]) together with the event the consumer's stream has to wait on.  SURVEY.md 8f row 1, second half."""
+    groundtruth [B,1,h,w]) together with the event the consumer's stream has to wait on.  SURVEY.md 8f row 1, second half.
+    native_groundtruth (datasets.groundtruth: native): the maps differ in size, so groundtruth is [B,1,Hmax,Wmax], each map zero-padded at
+    its bottom and right, and 'groundtruth_size' [B,2] int32 (host) holds every map's true (H, W)."""
 
-    def __init__(self, loader, img_height, img_width, device="cuda", depth=2):
+    def __init__(self, loader, img_height, img_width, device="cuda", depth=2, native_groundtruth=False):
         dev = torch.device(device)
         if dev.type == "cuda" and dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())          # the worker thread needs an explicit index
         self.loader, self.h, self.w, self.device, self.depth = loader, int(img_height), int(img_width), dev, depth
+        self.native_groundtruth = bool(native_groundtruth)
         self.transform = GpuImageTransform(img_height, img_width, dev)
 
     def __len__(self):
@@ -285,10 +299,20 @@ class PrefetchLoader:
             for shape, idx in groups.items():
                 out[idx] = self.transform(torch.stack([frames[i] for i in idx]))
             K = torch.stack([s['intrinsics'] for s in samples]).to(self.device, non_blocking=True)
-            gt = torch.stack([s['groundtruth'] for s in samples]).to(self.device, non_blocking=True)
+            extra = {}
+            if self.native_groundtruth:
+                maps = [s['groundtruth'] for s in samples]
+                sizes = torch.tensor([tuple(m.shape[-2:]) for m in maps], dtype=torch.int32)
+                host = torch.zeros((B, 1, int(sizes[:, 0].max()), int(sizes[:, 1].max())), dtype=torch.float32).pin_memory()
+                for i, m in enumerate(maps):
+                    host[i, :, :m.shape[-2], :m.shape[-1]] = m
+                gt = host.to(self.device, non_blocking=True)
+                extra['groundtruth_size'] = sizes
+            else:
+                gt = torch.stack([s['groundtruth'] for s in samples]).to(self.device, non_blocking=True)
             done = torch.cuda.Event()
             done.record(stream)
-        return {'tgt': out[:B], 'ref_imgs': [out[B:2 * B], out[2 * B:]], 'intrinsics': K, 'groundtruth': gt}, done
+        return dict({'tgt': out[:B], 'ref_imgs': [out[B:2 * B], out[2 * B:]], 'intrinsics': K, 'groundtruth': gt}, **extra), done
 
     def __iter__(self):
         import queue

@@ -6,6 +6,10 @@ numpy temporaries; only the ten result floats cross PCIe.  Differences from the 
 `disp_to_depth(pred[0]).cpu()` raises on the nested list it gets, evaluate.py:11-12) and 'sq_rel' is the squared-relative error
 (the reference stores rms under that key, evaluate.py:36).  `min_gt`: ground-truth values <= min_gt are skipped (sparse KITTI
 ground truth); the default -1 takes every element, as the reference does.
+
+`evaluate_depth(gt, pred, sizes, crop, ...)` is the KITTI protocol of monodepth2's evaluate_depth.py instead: per image, at the ground
+truth's own resolution, crop, depth range, per-image median scaling, metrics averaged over images (mcav_eval_depth; the definition is
+tests/eval_protocol_ref.py).  `reduce_rows` turns the per-image rows of several batches into that result with one read-back.
 """
 import torch
 
@@ -14,6 +18,8 @@ from mcav import lib as L
 L.register({
     "mcav_depth_metrics_workspace_bytes": (L.c_sz, []),
     "mcav_depth_metrics": (L.c_i, [L.c_p, L.c_p, L.c_sz, L.c_f, L.c_p, L.c_p, L.c_sz, L.c_p]),
+    "mcav_eval_depth_workspace_bytes": (L.c_sz, [L.c_i, L.c_i, L.c_i]),
+    "mcav_eval_depth": (L.c_i, [L.c_p, L.c_p] + [L.c_i] * 5 + [L.c_p, L.c_p, L.c_f, L.c_f, L.c_f, L.c_i, L.c_p, L.c_p, L.c_sz, L.c_p]),
 })
 
 KEYS = ("silog", "abs_rel", "log10", "rms", "sq_rel", "log_rms", "d1", "d2", "d3")
@@ -34,3 +40,93 @@ def compute_errors(gt, pred, min_gt=-1.0):
     acc = dict(zip(KEYS, vals[:9]))
     acc["count"] = int(vals[9])
     return acc
+
+
+EVAL_MEDIAN_SCALING = 1                        # include/mcav_depth.h MCAV_EVAL_MEDIAN_SCALING
+ROW_KEYS = KEYS + ("count", "ratio")
+# crop boxes as fractions of the true ground-truth size (monodepth evaluation_utils.py / monodepth2 evaluate_depth.py)
+CROPS = {"garg": (0.40810811, 0.99189189, 0.03594771, 0.96405229),
+         "eigen": (0.3324324, 0.91351351, 0.0359477, 0.96405229)}
+
+
+def crop_box(Hb, Wb, crop):
+    """-> (y0, y1, x0, x1), half-open.  crop: 'garg', 'eigen' (float64 products, truncated), None (the whole image) or an explicit box."""
+    if crop is None:
+        return (0, Hb, 0, Wb)
+    if isinstance(crop, str):
+        if crop not in CROPS:
+            raise L.MCAVError("evaluate_depth: crop must be 'garg', 'eigen', None or (y0, y1, x0, x1), got %r" % crop)
+        fy0, fy1, fx0, fx1 = CROPS[crop]
+        return (int(fy0 * Hb), int(fy1 * Hb), int(fx0 * Wb), int(fx1 * Wb))
+    box = tuple(int(v) for v in crop)
+    if len(box) != 4:
+        raise L.MCAVError("evaluate_depth: an explicit crop is (y0, y1, x0, x1), got %r" % (crop,))
+    return box
+
+
+def eval_depth_rows(gt, pred, sizes=None, crop="garg", min_depth=1e-3, max_depth=80.0, median_scaling=True, scale=1.0):
+    """The per-image rows [B, 11] (ROW_KEYS: the nine metrics, count, ratio) on the device; no read-back.  Arguments as evaluate_depth."""
+    disp = pred[0] if isinstance(pred, (list, tuple)) else pred
+    gt = L.dev(gt.detach().to(torch.float32).contiguous(), "gt")
+    disp = L.dev(disp.detach().to(torch.float32).contiguous(), "pred")
+    if gt.dim() == 4:
+        if gt.shape[1] != 1:
+            raise L.MCAVError("evaluate_depth: gt must be [B,1,Hg,Wg] or [B,Hg,Wg], got %s" % (tuple(gt.shape),))
+        gt = gt[:, 0]
+    if disp.dim() == 4:
+        if disp.shape[1] != 1:
+            raise L.MCAVError("evaluate_depth: the prediction must be [B,1,h,w] or [B,h,w], got %s" % (tuple(disp.shape),))
+        disp = disp[:, 0]
+    if gt.dim() != 3 or disp.dim() != 3 or gt.shape[0] != disp.shape[0]:
+        raise L.MCAVError("evaluate_depth: gt %s and prediction %s do not describe one batch" % (tuple(gt.shape), tuple(disp.shape)))
+    B, Hg, Wg = gt.shape
+    h, w = disp.shape[1:]
+    if sizes is None:
+        sizes = [(Hg, Wg)] * B
+    sizes = [tuple(int(v) for v in s) for s in (sizes.tolist() if hasattr(sizes, "tolist") else sizes)]
+    if len(sizes) != B or any(len(s) != 2 or not (1 <= s[0] <= Hg and 1 <= s[1] <= Wg) for s in sizes):
+        raise L.MCAVError("evaluate_depth: sizes must hold %d pairs (Hb, Wb) with 1 <= Hb <= %d, 1 <= Wb <= %d, got %r" % (B, Hg, Wg, sizes))
+    per_image = isinstance(crop, (list, tuple)) and len(crop) == B and len(crop) > 0 and isinstance(crop[0], (list, tuple))
+    boxes = [crop_box(Hb, Wb, crop[b] if per_image else crop) for b, (Hb, Wb) in enumerate(sizes)]
+    if not (float(min_depth) > 0 and float(max_depth) > float(min_depth)):
+        raise L.MCAVError("evaluate_depth: need 0 < min_depth < max_depth, got %r, %r" % (min_depth, max_depth))
+    dev = gt.device
+    meta = torch.tensor([v for s in sizes for v in s] + [v for bx in boxes for v in bx], dtype=torch.int32).to(dev)
+    rows = torch.empty((B, 11), dtype=torch.float32, device=dev)
+    h_ = L.lib()
+    ws = L.workspace(h_.mcav_eval_depth_workspace_bytes(B, Hg, Wg), dev, "eval_depth")
+    flags = EVAL_MEDIAN_SCALING if median_scaling else 0
+    L.check(h_.mcav_eval_depth(L.ptr(gt), L.ptr(disp), B, Hg, Wg, h, w, L.ptr(meta), L.c_p(meta.data_ptr() + 4 * 2 * B),
+                               float(min_depth), float(max_depth), float(scale), flags, L.ptr(rows), L.ptr(ws), ws.numel(), L.stream()),
+            "mcav_eval_depth")
+    return rows
+
+
+def reduce_rows(rows):
+    """Per-image rows (one [B, 11] tensor or a list of them, e.g. one per batch) -> the protocol's result: the mean of every metric over
+    the images with count > 0, 'images', the total pixel 'count', and monodepth2's scale statistics 'ratio_median' = median(ratios),
+    'ratio_std' = std(ratios / ratio_median).  The rows are joined on the device and read back once."""
+    import numpy as np
+    if isinstance(rows, (list, tuple)):
+        rows = torch.cat(list(rows)) if rows else torch.empty((0, 11))
+    r = rows.detach().cpu().numpy().astype(np.float64).reshape(-1, 11)
+    valid = r[:, 9] > 0
+    out = {k: float(np.mean(r[valid, i])) if valid.any() else float("nan") for i, k in enumerate(KEYS)}
+    out["images"] = int(valid.sum())
+    out["count"] = int(r[valid, 9].sum())
+    ratios = r[valid, 10]
+    med = float(np.median(ratios)) if ratios.size else float("nan")
+    out["ratio_median"] = med
+    out["ratio_std"] = float(np.std(ratios / med)) if ratios.size else float("nan")
+    return out
+
+
+def evaluate_depth(gt, pred, sizes=None, crop="garg", min_depth=1e-3, max_depth=80.0, median_scaling=True, scale=1.0, per_image=False):
+    """The KITTI depth protocol (monodepth2 evaluate_depth.py) on the GPU.
+    gt: [B,1,Hg,Wg] or [B,Hg,Wg] ground-truth depth in metres (0 = no return), zero-padded to the batch's largest image; pred: the
+    network's sigmoid disparity as compute_errors takes it ([B,1,h,w] / [B,h,w], or a list whose first entry it is).  sizes: the true
+    (Hb, Wb) of every image (host; default: (Hg, Wg)).  crop: 'garg', 'eigen', None, an explicit (y0, y1, x0, x1) or a list of B of
+    them.  scale: monodepth2's pred_depth_scale_factor.  -> the dict of reduce_rows; with per_image=True also the [B, 11] device rows."""
+    rows = eval_depth_rows(gt, pred, sizes, crop, min_depth, max_depth, median_scaling, scale)
+    out = reduce_rows(rows)
+    return (out, rows) if per_image else out

@@ -78,6 +78,7 @@ class Trainer:
         self.criterion.automask = bool((config.get('loss') or {}).get('automask', False))                   # and identity auto-masking
         self.criterion.edge_aware_smoothness = bool((config.get('loss') or {}).get('edge_aware_smoothness', False))   # monodepth2's smoothness
         self.criterion.edge_smoothness_weight = float((config.get('loss') or {}).get('edge_smoothness_weight', 1e-3))
+        self.validation = self.validation_config(config.get('validation'))      # opt-in KITTI protocol for validate()
         from mcav.streams import Branch
         self.pose_branch = Branch()
         self.loss = None
@@ -138,13 +139,15 @@ class Trainer:
         if getattr(self.dataset, "raw", False):
             # file-backed samples decoded to uint8 on the host (worker processes); resize + normalise on the GPU, one batch ahead
             from dataloaders import PrefetchLoader, raw_collate
-            mk = lambda idx: PrefetchLoader(torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size, sampler=SequentialIndicesSampler(idx),
-                                                                        num_workers=self.num_workers, drop_last=True, collate_fn=raw_collate),
-                                            self.dataset.img_height, self.dataset.img_width, self.device)
-            return mk(train_indices), mk(val_indices)
-        mk = lambda idx: torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size, sampler=SequentialIndicesSampler(idx),
-                                                     num_workers=self.num_workers, drop_last=True, pin_memory=True)
-        return mk(train_indices), mk(val_indices)
+            native = bool(getattr(self.dataset, "native_gt", False))
+            mk = lambda idx, drop: PrefetchLoader(torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size,
+                                                                              sampler=SequentialIndicesSampler(idx), num_workers=self.num_workers,
+                                                                              drop_last=drop, collate_fn=raw_collate),
+                                                  self.dataset.img_height, self.dataset.img_width, self.device, native_groundtruth=native)
+            return mk(train_indices, True), mk(val_indices, self.validation is None)    # the protocol scores every validation image
+        mk = lambda idx, drop: torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size, sampler=SequentialIndicesSampler(idx),
+                                                           num_workers=self.num_workers, drop_last=drop, pin_memory=True)
+        return mk(train_indices, True), mk(val_indices, self.validation is None)
 
     def set_train(self):
         self.depth_model.train()
@@ -252,8 +255,51 @@ class Trainer:
         loss = self.criterion.forward(tgt, ref_imgs, disps, poses, intrinsics, gt)
         return [disps, poses], loss
 
+    VALIDATION_DEFAULTS = {'protocol': 'eigen', 'crop': 'garg', 'min_depth': 1e-3, 'max_depth': 80.0, 'median_scaling': True, 'scale': 1.0}
+
+    @classmethod
+    def validation_config(cls, cfg):
+        """The top-level config key `validation` (None: validate() keeps the reference's per-batch compute_errors).  Its keys and defaults:
+        protocol: eigen, crop: garg (or eigen, or null = whole image), min_depth: 1e-3, max_depth: 80, median_scaling: true, scale: 1.0."""
+        if cfg is None:
+            return None
+        unknown = set(cfg) - set(cls.VALIDATION_DEFAULTS)
+        if unknown:
+            raise ValueError("config validation: unknown keys %s (known: %s)" % (sorted(unknown), sorted(cls.VALIDATION_DEFAULTS)))
+        v = dict(cls.VALIDATION_DEFAULTS, **cfg)
+        if v['protocol'] != 'eigen':
+            raise ValueError("config validation.protocol: only 'eigen' (monodepth2's KITTI protocol) is implemented, got %r" % (v['protocol'],))
+        if v['crop'] not in ('garg', 'eigen', None):
+            raise ValueError("config validation.crop must be garg, eigen or null, got %r" % (v['crop'],))
+        v['min_depth'], v['max_depth'], v['scale'] = float(v['min_depth']), float(v['max_depth']), float(v['scale'])
+        v['median_scaling'] = bool(v['median_scaling'])
+        return v
+
+    @torch.no_grad()
+    def validate_protocol(self):
+        """validate() with the `validation` key: the KITTI protocol (evaluate.evaluate_depth) over the WHOLE validation loader.  Only the
+        depth network runs, in eval mode, on 'tgt'; the per-image rows stay on the device and are reduced with one read-back."""
+        from evaluate import eval_depth_rows, reduce_rows
+        v = self.validation
+        self.depth_model.eval()
+        rows = []
+        try:
+            for samples in self.validation_loader:
+                if 'groundtruth_size' not in samples:
+                    raise ValueError("validation: the KITTI protocol needs the native ground truth (datasets.groundtruth: native with a KITTI "
+                                     "split); this loader gives ground truth resized to the network's input")
+                tgt = samples['tgt'].to(self.device, non_blocking=True)
+                gt = samples['groundtruth'].to(self.device, non_blocking=True)
+                rows.append(eval_depth_rows(gt, self.depth_model(tgt), samples['groundtruth_size'], v['crop'], v['min_depth'], v['max_depth'],
+                                            v['median_scaling'], v['scale']))
+        finally:
+            self.set_train()
+        return reduce_rows(rows)
+
     @torch.no_grad()
     def validate(self):
+        if self.validation is not None:
+            return self.validate_protocol()
         from evaluate import compute_errors
         self.set_eval()
         acc = None
