@@ -218,6 +218,45 @@ int mcav_image_preprocess(const unsigned char* src_bhwc, int B, int H0, int W0, 
                           const int* vbounds, const int* vkk, int vksize, const float* mean3, const float* std3, float* dst_bchw,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* Training-time augmentation (monodepth2): mcav_image_preprocess plus a horizontal flip and torchvision's ColorJitter on Pillow images, per
+ * frame.  The definition is tests/augment_ref.py.  For frame b with record rec = records[b] and R = the resized uint8 image of
+ * mcav_image_preprocess (bit-exact against Pillow's resize):
+ *   MCAV_AUG_FLIP:   R = R[:, ::-1]  (equal to Pillow's transpose(FLIP_LEFT_RIGHT) before the resize)
+ *   plain[b]       = Normalize(R / 255)
+ *   MCAV_AUG_COLOUR: the operations rec.order[0..3] in that order, each uint8 -> uint8 as Pillow; an entry above 3 is skipped
+ *     BRIGHTNESS(f) = blend(0, R, f)              SATURATION(f) = blend(L(R), R, f)        (ImageEnhance.Brightness / Color)
+ *     CONTRAST(f)   = blend(int(S / n + 0.5), R, f), S = the integer sum of L over the frame as it stands at that point (ImageEnhance.Contrast)
+ *     HUE(shift)    = RGB -> HSV (Pillow), H = (H + shift) mod 256, HSV -> RGB (Pillow)   (torchvision F_pil.adjust_hue)
+ *     with L(p) = (19595 r + 38470 g + 7471 b + 0x8000) >> 16 and blend(a, b, f) = ImagingBlend in float32.
+ *   aug[b]         = Normalize(R / 255)   (equal to plain[b] without MCAV_AUG_COLOUR)
+ * records: DEVICE array of B records (the caller repeats a sample's record for its frames).  Unknown flag bits are ignored and hue_shift is
+ * taken mod 256, so no record reads or writes out of bounds.  plain, aug: device float [B,3,h,w].  The other arguments and the resample
+ * tables as mcav_image_preprocess.  Deterministic: integer sums only (one 64-bit atomic per workgroup), outputs bit-identical from run to
+ * run; no host synchronisation, allocation or copy (one hipMemsetAsync of the sums): the call can be captured.  4 launches.
+ * Workspace (mcav_image_augment_workspace_bytes, each piece rounded up to 256 bytes): B * H0 * w * 3 + B * h * w * 4 + B * 8 bytes.
+ * Returns MCAV_E_INVALID for a null pointer, a non-positive size or B > 65535, MCAV_E_WORKSPACE for a workspace below
+ * mcav_image_augment_workspace_bytes(B, H0, h, w); nothing is launched then. */
+#define MCAV_AUG_FLIP 1
+#define MCAV_AUG_COLOUR 2
+#define MCAV_AUG_OP_BRIGHTNESS 0
+#define MCAV_AUG_OP_CONTRAST 1
+#define MCAV_AUG_OP_SATURATION 2
+#define MCAV_AUG_OP_HUE 3
+#define MCAV_AUG_OP_NONE 255
+typedef struct mcav_augment_record {
+    int32_t flags;              /* MCAV_AUG_FLIP | MCAV_AUG_COLOUR */
+    uint8_t order[4];           /* MCAV_AUG_OP_* in the order applied (torchvision's random permutation) */
+    float brightness;           /* blend factors, float32 as ImagingBlend takes them */
+    float contrast;
+    float saturation;
+    int32_t hue_shift;          /* trunc(hue_factor * 255) mod 256 */
+} mcav_augment_record;          /* 24 bytes */
+size_t mcav_image_augment_workspace_bytes(int B, int H0, int h, int w);
+int mcav_image_preprocess_augment(const unsigned char* src_bhwc, int B, int H0, int W0, int h, int w, const int* hbounds, const int* hkk,
+                                  int hksize, const int* vbounds, const int* vkk, int vksize, const float* mean3, const float* std3,
+                                  const mcav_augment_record* records, float* plain_bchw, float* aug_bchw, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,14 @@ __global__ __launch_bounds__(256) void pp_vertical_kernel(const uint8_t* __restr
     }
 }
 
+// The horizontal pass on its own, for mcav_image_preprocess_augment (augment.hip).
+void pp_launch_horizontal(const uint8_t* src, int B, int H0, int W0, int w, const int* hbounds, const int* hkk, int hksize, uint8_t* tmp,
+                          hipStream_t s) {
+    const size_t n1 = (size_t)B * H0 * w;
+    const int g1 = (int)((n1 + 255) / 256 < 8192 ? (n1 + 255) / 256 : 8192);
+    pp_horizontal_kernel<<<g1, 256, 0, s>>>(src, B, H0, W0, w, hbounds, hkk, hksize, tmp);
+}
+
 }  // namespace mcav
 
 using namespace mcav;

@@ -8,6 +8,8 @@ training step consumes is kept: a dict with 'tgt' [3,H,W], 'ref_imgs' [2 x [3,H,
 'groundtruth' [1,H,W] (reference dataloaders.py:226-251).  SyntheticTriplets produces such samples from a seed.
 `datasets.groundtruth: native` (opt-in, for evaluate.evaluate_depth): the ground truth stays at its own size, in metres, and PrefetchLoader
 zero-pads each batch to its largest map and adds 'groundtruth_size' [B,2] int32 (host).  The loss never reads the ground truth.
+`datasets.augmentation.color_jitter` / `.flip` (opt-in, Augmentation): monodepth2's training-time colour jitter and horizontal flip, on the
+GPU with the resize; the training batches then also carry 'tgt_aug', 'ref_imgs_aug' (what the networks see) and 'augment_records'.
 """
 import ctypes
 
@@ -70,6 +72,35 @@ class GpuImageTransform:
                                         L.ptr(out), L.ptr(ws), ws.numel(), L.stream()), "mcav_image_preprocess")
         return out[0] if single else out
 
+    def augmented(self, img_u8, records):
+        """The same chain plus a per-frame flip and colour jitter (Augmentation; include/mcav_depth.h: mcav_image_preprocess_augment).
+        img_u8: uint8 [B, H0, W0, 3]; records: B host records (AUGMENT_RECORD).  -> (plain, aug) float32 [B, 3, h, w] on the device: plain is
+        __call__'s output, mirrored where the record flips; aug is what the networks see."""
+        from mcav import lib as L
+        x = img_u8
+        if x.dim() != 4 or x.dtype != torch.uint8 or x.shape[-1] != 3:
+            raise L.MCAVError("GpuImageTransform.augmented: expected uint8 [B, H, W, 3], got %s %s" % (x.dtype, tuple(x.shape)))
+        records = np.ascontiguousarray(records, dtype=AUGMENT_RECORD)
+        if records.shape != (x.shape[0],):
+            raise L.MCAVError("GpuImageTransform.augmented: %d frames but %s records" % (x.shape[0], records.shape))
+        if not x.is_cuda:
+            x = x.contiguous().pin_memory().to(self.device, non_blocking=True)
+        x = x.contiguous()
+        rec = torch.from_numpy(records.view(np.uint8)).pin_memory().to(x.device, non_blocking=True)
+        B, H0, W0, _ = x.shape
+        hb, hk, hks = self._axis(W0, self.w)
+        vb, vk, vks = self._axis(H0, self.h)
+        h = L.lib()
+        ws = L.workspace(h.mcav_image_augment_workspace_bytes(B, H0, self.h, self.w), x.device, "augment")
+        plain = torch.empty((B, 3, self.h, self.w), dtype=torch.float32, device=x.device)
+        aug = torch.empty_like(plain)
+        mean = (ctypes.c_float * 3)(*self.MEAN)
+        std = (ctypes.c_float * 3)(*self.STD)
+        L.check(h.mcav_image_preprocess_augment(L.ptr(x), B, H0, W0, self.h, self.w, L.ptr(hb), L.ptr(hk), hks, L.ptr(vb), L.ptr(vk), vks,
+                                                mean, std, L.ptr(rec), L.ptr(plain), L.ptr(aug), L.ptr(ws), ws.numel(), L.stream()),
+                "mcav_image_preprocess_augment")
+        return plain, aug
+
     def scale_intrinsics(self, K, og_h, og_w):
         """dataloaders.py:95-98 -- on a COPY: the reference scales the cached sample's matrix in place on every fetch."""
         K = torch.as_tensor(K, dtype=torch.float64).clone()
@@ -85,10 +116,93 @@ def _register():
         "mcav_image_preprocess_workspace_bytes": (L.c_sz, [L.c_i, L.c_i, L.c_i]),
         "mcav_image_preprocess": (L.c_i, [L.c_p, L.c_i, L.c_i, L.c_i, L.c_i, L.c_i, L.c_p, L.c_p, L.c_i, L.c_p, L.c_p, L.c_i, L.c_p, L.c_p, L.c_p,
                                           L.c_p, L.c_sz, L.c_p]),
+        "mcav_image_augment_workspace_bytes": (L.c_sz, [L.c_i, L.c_i, L.c_i, L.c_i]),
+        "mcav_image_preprocess_augment": (L.c_i, [L.c_p, L.c_i, L.c_i, L.c_i, L.c_i, L.c_i, L.c_p, L.c_p, L.c_i, L.c_p, L.c_p, L.c_i, L.c_p,
+                                                  L.c_p, L.c_p, L.c_p, L.c_p, L.c_p, L.c_sz, L.c_p]),
     })
 
 
 _register()
+
+
+# ------------------------------------------------------------------------------------------------ training-time augmentation (monodepth2)
+AUGMENT_RECORD = np.dtype([("flags", "<i4"), ("order", "u1", (4,)), ("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"),
+                           ("hue_shift", "<i4")])          # include/mcav_depth.h: mcav_augment_record
+AUG_FLIP, AUG_COLOUR = 1, 2
+AUG_OP_NONE = 255
+
+
+class Augmentation:
+    """monodepth2's training-time augmentation: a horizontal flip with probability p_flip and torchvision's ColorJitter (brightness,
+    contrast, saturation from U[max(0, 1 - x), 1 + x], hue from U[-x, x], in a random order) with probability p_color, one record per sample
+    for all its frames.  The networks see the augmented frames, the loss the plain ones (mirrored with the flip).
+
+    Records are drawn on the host from Generator(PCG64(SeedSequence([seed, rank, epoch]))) in batch order, ten uniforms per sample whatever
+    the probabilities: the stream depends on (seed, rank, epoch) only, not on num_workers, and a resumed epoch draws it again.
+    A jitter range of 0 leaves its operation out (torchvision passes None then); the flip of the intrinsics is PrefetchLoader's."""
+    JITTER_DEFAULTS = {'brightness': 0.2, 'contrast': 0.2, 'saturation': 0.2, 'hue': 0.1, 'p': 0.5}
+    CONFIG_KEYS = ('image_width', 'image_height', 'shuffle', 'color_jitter', 'flip')
+
+    def __init__(self, brightness=0.2, contrast=0.2, saturation=0.2, hue=0.1, p_color=0.5, p_flip=0.5, seed=0, rank=0):
+        self.brightness, self.contrast, self.saturation, self.hue = float(brightness), float(contrast), float(saturation), float(hue)
+        self.p_color, self.p_flip, self.seed, self.rank = float(p_color), float(p_flip), int(seed), int(rank)
+        for name in ('brightness', 'contrast', 'saturation', 'hue'):
+            v = getattr(self, name)
+            if not np.isfinite(v) or v < 0:
+                raise ValueError("augmentation: color_jitter.%s must be a finite number >= 0, got %r" % (name, v))
+        if self.hue > 0.5:
+            raise ValueError("augmentation: color_jitter.hue must be at most 0.5, got %r" % (self.hue,))
+        for name in ('p_color', 'p_flip'):
+            v = getattr(self, name)
+            if not 0.0 <= v <= 1.0:
+                raise ValueError("augmentation: probability %s must lie in [0, 1], got %r" % (name, v))
+
+    @classmethod
+    def from_config(cls, config, rank=0):
+        """datasets.augmentation.color_jitter {brightness, contrast, saturation, hue, p} and datasets.augmentation.flip (a probability).
+        None when neither key is there: the loader then behaves as before.  A key left out of color_jitter takes monodepth2's value; with only
+        one of the two keys, the other operation is off."""
+        aug = config['datasets']['augmentation']
+        unknown = set(aug) - set(cls.CONFIG_KEYS)
+        if unknown:
+            raise ValueError("config datasets.augmentation: unknown keys %s (known: %s)" % (sorted(unknown), list(cls.CONFIG_KEYS)))
+        if 'color_jitter' not in aug and 'flip' not in aug:
+            return None
+        if config['datasets'].get('dataset', ['KITTI']) == ['synthetic']:
+            raise ValueError("config datasets.augmentation: color_jitter / flip need decoded images; the synthetic triplets are normalised "
+                             "floats")
+        cj = aug.get('color_jitter')
+        if cj is None:
+            cj = dict(cls.JITTER_DEFAULTS, p=0.0)
+        if not isinstance(cj, dict):
+            raise ValueError("config datasets.augmentation.color_jitter must be a mapping, got %r" % (cj,))
+        unknown = set(cj) - set(cls.JITTER_DEFAULTS)
+        if unknown:
+            raise ValueError("config datasets.augmentation.color_jitter: unknown keys %s (known: %s)" % (sorted(unknown), list(cls.JITTER_DEFAULTS)))
+        cj = dict(cls.JITTER_DEFAULTS, **cj)
+        return cls(cj['brightness'], cj['contrast'], cj['saturation'], cj['hue'], p_color=cj['p'], p_flip=aug.get('flip', 0.0),
+                   seed=int(config['action'].get('random_seed', 0)), rank=rank)
+
+    def generator(self, epoch):
+        return np.random.Generator(np.random.PCG64(np.random.SeedSequence([self.seed, self.rank, int(epoch)])))
+
+    def draw(self, rng, n):
+        """The next n records (AUGMENT_RECORD) of the stream."""
+        u = rng.random((n, 10))
+        rec = np.zeros(n, AUGMENT_RECORD)
+        rec['flags'] = np.where(u[:, 0] < self.p_flip, AUG_FLIP, 0) | np.where(u[:, 1] < self.p_color, AUG_COLOUR, 0)
+        for col, name in ((2, 'brightness'), (3, 'contrast'), (4, 'saturation')):
+            x = getattr(self, name)
+            lo, hi = max(0.0, 1.0 - x), 1.0 + x
+            rec[name] = (lo + (hi - lo) * u[:, col]).astype(np.float32)
+        hue = -self.hue + 2.0 * self.hue * u[:, 5]
+        rec['hue_shift'] = np.trunc(hue * 255.0).astype(np.int64) % 256          # torchvision: np.int8(hue_factor * 255).view(np.uint8)
+        order = np.argsort(u[:, 6:10], axis=1, kind='stable').astype(np.uint8)  # torchvision: torch.randperm(4) over (b, c, s, h)
+        for op, x in enumerate((self.brightness, self.contrast, self.saturation, self.hue)):
+            if x == 0:
+                order[order == op] = AUG_OP_NONE
+        rec['order'] = order
+        return rec
 
 
 class SyntheticTriplets(Dataset):
@@ -275,33 +389,59 @@ class PrefetchLoader:
     and hands the trainer finished batches in the reference's collated layout (tgt [B,3,h,w], ref_imgs 2 x [B,3,h,w], intrinsics [B,3,3] fp64,
     groundtruth [B,1,h,w]) together with the event the consumer's stream has to wait on.  SURVEY.md 8f row 1, second half.
     native_groundtruth (datasets.groundtruth: native): the maps differ in size, so groundtruth is [B,1,Hmax,Wmax], each map zero-padded at
-    its bottom and right, and 'groundtruth_size' [B,2] int32 (host) holds every map's true (H, W)."""
+    its bottom and right, and 'groundtruth_size' [B,2] int32 (host) holds every map's true (H, W).
+    augment (an Augmentation): each batch also carries 'tgt_aug', 'ref_imgs_aug' (what the networks see) and 'augment_records' (host, one
+    AUGMENT_RECORD per sample); a flipped sample's frames, ground truth (within its true size) and principal point (cx' = w - 1 - cx: the
+    warp samples pixel centres 0..w-1) are mirrored.  Call set_epoch(epoch) before each pass: the records are drawn for (seed, rank, epoch)."""
 
-    def __init__(self, loader, img_height, img_width, device="cuda", depth=2, native_groundtruth=False):
+    def __init__(self, loader, img_height, img_width, device="cuda", depth=2, native_groundtruth=False, augment=None):
         dev = torch.device(device)
         if dev.type == "cuda" and dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())          # the worker thread needs an explicit index
         self.loader, self.h, self.w, self.device, self.depth = loader, int(img_height), int(img_width), dev, depth
         self.native_groundtruth = bool(native_groundtruth)
         self.transform = GpuImageTransform(img_height, img_width, dev)
+        self.augment = augment
+        self.epoch = 0
 
     def __len__(self):
         return len(self.loader)
 
-    def _finish(self, samples, stream):
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def _finish(self, samples, stream, rng=None):
         B = len(samples)
         frames = [s['tgt'] for s in samples] + [s['ref_imgs'][0] for s in samples] + [s['ref_imgs'][1] for s in samples]
         out = torch.empty((3 * B, 3, self.h, self.w), dtype=torch.float32, device=self.device)
+        extra = {}
+        flip = np.zeros(B, bool)
+        if rng is not None:
+            recs = self.augment.draw(rng, B)
+            flip = (recs['flags'] & AUG_FLIP) != 0
+            frame_recs = np.concatenate([recs] * 3)
+            out_aug = torch.empty_like(out)
+            extra['augment_records'] = recs
         with torch.cuda.stream(stream):
             groups = {}
             for i, f in enumerate(frames):
                 groups.setdefault(tuple(f.shape), []).append(i)
             for shape, idx in groups.items():
-                out[idx] = self.transform(torch.stack([frames[i] for i in idx]))
-            K = torch.stack([s['intrinsics'] for s in samples]).to(self.device, non_blocking=True)
-            extra = {}
+                if rng is None:
+                    out[idx] = self.transform(torch.stack([frames[i] for i in idx]))
+                else:
+                    out[idx], out_aug[idx] = self.transform.augmented(torch.stack([frames[i] for i in idx]), frame_recs[idx])
+            K = torch.stack([s['intrinsics'] for s in samples])
+            if flip.any():
+                f = torch.from_numpy(flip)
+                K = K.clone()
+                K[f, 0, 2] = (self.w - 1) - K[f, 0, 2]
+                K[f, 0, 1] = -K[f, 0, 1]
+            K = K.to(self.device, non_blocking=True)
+            if rng is not None:
+                extra['tgt_aug'], extra['ref_imgs_aug'] = out_aug[:B], [out_aug[B:2 * B], out_aug[2 * B:]]
             if self.native_groundtruth:
-                maps = [s['groundtruth'] for s in samples]
+                maps = [s['groundtruth'].flip(-1) if flip[i] else s['groundtruth'] for i, s in enumerate(samples)]
                 sizes = torch.tensor([tuple(m.shape[-2:]) for m in maps], dtype=torch.int32)
                 host = torch.zeros((B, 1, int(sizes[:, 0].max()), int(sizes[:, 1].max())), dtype=torch.float32).pin_memory()
                 for i, m in enumerate(maps):
@@ -309,7 +449,8 @@ class PrefetchLoader:
                 gt = host.to(self.device, non_blocking=True)
                 extra['groundtruth_size'] = sizes
             else:
-                gt = torch.stack([s['groundtruth'] for s in samples]).to(self.device, non_blocking=True)
+                gt = torch.stack([s['groundtruth'].flip(-1) if flip[i] else s['groundtruth'] for i, s in enumerate(samples)])
+                gt = gt.to(self.device, non_blocking=True)
             done = torch.cuda.Event()
             done.record(stream)
         return dict({'tgt': out[:B], 'ref_imgs': [out[B:2 * B], out[2 * B:]], 'intrinsics': K, 'groundtruth': gt}, **extra), done
@@ -320,12 +461,13 @@ class PrefetchLoader:
         q = queue.Queue(maxsize=self.depth)
         stream = torch.cuda.Stream(device=self.device)
         dev = self.device
+        rng = self.augment.generator(self.epoch) if self.augment is not None else None      # drawn in batch order, in this thread
 
         def work():
             try:
                 torch.cuda.set_device(dev)
                 for samples in self.loader:
-                    q.put(self._finish(samples, stream))
+                    q.put(self._finish(samples, stream, rng))
                 q.put(None)
             except BaseException as e:          # surface loader errors in the consumer
                 q.put(e)
@@ -339,7 +481,8 @@ class PrefetchLoader:
                 raise item
             batch, done = item
             torch.cuda.current_stream(self.device).wait_event(done)
-            for v in [batch['tgt']] + batch['ref_imgs'] + [batch['intrinsics'], batch['groundtruth']]:
+            for v in [batch['tgt']] + batch['ref_imgs'] + [batch['intrinsics'], batch['groundtruth']] + \
+                    ([batch['tgt_aug']] + batch['ref_imgs_aug'] if 'tgt_aug' in batch else []):
                 v.record_stream(torch.cuda.current_stream(self.device))
             yield batch
         t.join()

@@ -89,10 +89,15 @@ class Trainer:
         else:
             self.load_chkpnt()
 
+        from dataloaders import Augmentation
+        self.augmentation = Augmentation.from_config(config, self.rank)     # opt-in colour jitter + flip of the training batches
         if dataset is None:
             from dataloaders import UnSupKittiDataset
             dataset = UnSupKittiDataset(config, transforms=None)
         self.dataset = dataset
+        if self.augmentation is not None and not getattr(dataset, "raw", False):
+            raise ValueError("config datasets.augmentation: color_jitter / flip run on the GPU loader's decoded bytes; this dataset gives "
+                             "finished tensors")
         self.train_loader, self.validation_loader = self.create_loaders(act['random_seed'], act['split'][1])
         self.save_checkpoints = act.get('save_checkpoints', True)
 
@@ -140,11 +145,14 @@ class Trainer:
             # file-backed samples decoded to uint8 on the host (worker processes); resize + normalise on the GPU, one batch ahead
             from dataloaders import PrefetchLoader, raw_collate
             native = bool(getattr(self.dataset, "native_gt", False))
-            mk = lambda idx, drop: PrefetchLoader(torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size,
-                                                                              sampler=SequentialIndicesSampler(idx), num_workers=self.num_workers,
-                                                                              drop_last=drop, collate_fn=raw_collate),
-                                                  self.dataset.img_height, self.dataset.img_width, self.device, native_groundtruth=native)
-            return mk(train_indices, True), mk(val_indices, self.validation is None)    # the protocol scores every validation image
+            mk = lambda idx, drop, aug=None: PrefetchLoader(torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size,
+                                                                                      sampler=SequentialIndicesSampler(idx),
+                                                                                      num_workers=self.num_workers, drop_last=drop,
+                                                                                      collate_fn=raw_collate),
+                                                          self.dataset.img_height, self.dataset.img_width, self.device,
+                                                          native_groundtruth=native, augment=aug)
+            # the protocol scores every validation image; only the training batches are augmented
+            return mk(train_indices, True, self.augmentation), mk(val_indices, self.validation is None)
         mk = lambda idx, drop: torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size, sampler=SequentialIndicesSampler(idx),
                                                            num_workers=self.num_workers, drop_last=drop, pin_memory=True)
         return mk(train_indices, True), mk(val_indices, self.validation is None)
@@ -172,18 +180,23 @@ class Trainer:
         tgt = samples['tgt'].to(dev, non_blocking=True)
         ref_imgs = [img.to(dev, non_blocking=True) for img in samples['ref_imgs']]
         K = samples['intrinsics'].to(dev, non_blocking=True)
+        aug = [samples['tgt_aug']] + list(samples['ref_imgs_aug']) if 'tgt_aug' in samples else []
+        aug = [img.to(dev, non_blocking=True) for img in aug]          # augmentation: the networks' inputs, three more graph inputs
         if self._graphs is None:
             from mcav.graph import StepGraphs
 
-            def fwd_bwd(tgt, ref0, ref1, K):
+            def fwd_bwd(tgt, ref0, ref1, K, *aug):
                 self.model_optimizer.zero_grad()
-                _, loss = self.process_batch({'tgt': tgt, 'ref_imgs': [ref0, ref1], 'intrinsics': K, 'groundtruth': None})
+                batch = {'tgt': tgt, 'ref_imgs': [ref0, ref1], 'intrinsics': K, 'groundtruth': None}
+                if aug:
+                    batch.update(tgt_aug=aug[0], ref_imgs_aug=[aug[1], aug[2]])
+                _, loss = self.process_batch(batch)
                 sum(loss).backward()
                 return tuple(loss)
             buffers = list(self.depth_model.buffers()) + list(self.pose_model.buffers())
             self._graphs = StepGraphs(fwd_bwd, self.model_optimizer, capture_adam=not mdist.parallel(), buffers=buffers)
         self.model_optimizer.grad_scale = 1.0 / self.world
-        self.loss = list(self._graphs(tgt, ref_imgs[0], ref_imgs[1], K))
+        self.loss = list(self._graphs(tgt, ref_imgs[0], ref_imgs[1], K, *aug))
         if mdist.parallel():      # the buckets' collectives are already in flight behind the replaying graph (mcav/graph.py); remainder, wait, Adam
             self.model_optimizer.grad_scale = mdist.allreduce_gradients(self.model_optimizer.arena())
             self.model_optimizer.step()
@@ -215,6 +228,8 @@ class Trainer:
         return outputs, self.loss
 
     def run_epoch(self):
+        if hasattr(self.train_loader, "set_epoch"):
+            self.train_loader.set_epoch(self.epoch)      # the augmentation records are drawn for (seed, rank, epoch)
         for batch_indx, samples in enumerate(self.train_loader):
             self.train_step(samples)
             if self.step == 1:
@@ -235,21 +250,24 @@ class Trainer:
         ref_imgs = [img.to(dev, non_blocking=True) for img in samples['ref_imgs']]
         intrinsics = samples['intrinsics'].to(dev, non_blocking=True)
         gt = samples['groundtruth']
+        # augmented batches (PrefetchLoader with an Augmentation): the networks see the jittered frames, the loss the plain ones
+        net_tgt = samples['tgt_aug'].to(dev, non_blocking=True) if 'tgt_aug' in samples else tgt
+        net_refs = [img.to(dev, non_blocking=True) for img in samples['ref_imgs_aug']] if 'ref_imgs_aug' in samples else ref_imgs
         overlap = tgt.is_cuda and not semi_sup_pose
         if overlap:        # the pose net is independent of the depth net until the loss: second HIP stream (mcav/streams.py)
             from mcav import nn as mnn
             mnn.refresh_packed_weights(tgt.device)      # both streams read the packed filters: refresh them before the fork
-            poses = self.pose_branch.fork(self.pose_model, tgt, ref_imgs)
+            poses = self.pose_branch.fork(self.pose_model, net_tgt, net_refs)
         if hasattr(self.depth_model, "forward_pair"):
-            disps = list(self.depth_model.forward_pair(tgt, ref_imgs[0]))          # == two separate passes (per-pass BN statistics)
+            disps = list(self.depth_model.forward_pair(net_tgt, net_refs[0]))          # == two separate passes (per-pass BN statistics)
         else:
-            disps = [self.depth_model(image_t) for image_t in (tgt, ref_imgs[0])]  # two separate passes, as the reference
+            disps = [self.depth_model(image_t) for image_t in (net_tgt, net_refs[0])]  # two separate passes, as the reference
         if semi_sup_pose:
             poses = torch.cat((samples["oxts"][0].unsqueeze(1), samples["oxts"][1].unsqueeze(1)), 1).to(dev)
         elif overlap:
             poses = self.pose_branch.join(poses)
         else:
-            poses = self.pose_model(tgt, ref_imgs)
+            poses = self.pose_model(net_tgt, net_refs)
         if warp_test:
             return [disps, poses]
         loss = self.criterion.forward(tgt, ref_imgs, disps, poses, intrinsics, gt)
