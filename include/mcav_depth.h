@@ -85,6 +85,33 @@ int mcav_warp_loss_masked_fwd_bwd(const float* tgt, const float* ref0, const flo
                                   void* workspace, size_t workspace_bytes, void* stream,
                                   unsigned char* selection, size_t selection_bytes);
 
+/* Mono + stereo ("MS", monodepth2): mcav_warp_loss_masked_fwd_bwd with one more source view, the stereo frame of the target, warped into the
+ * target with depth(tgt), the same K and the FIXED transform [I | (-b, 0, 0)].  The known metric baseline b pins the scale of the depth (and
+ * of the pose net's translations) to metres.  e_s / i_s: the stereo warp's error and the unwarped stereo frame's error against tgt.
+ *   plain:                 loss_mam = tw0 mean e_0 + tw1 mean e_1 + tws mean e_s + tw2 mean e_2
+ *   MIN_REPROJ:            (tw0 + tw1 + tws) mean_p min(e_0, e_1, e_s) + warp 2 as in the masked entry
+ *   MIN_REPROJ + AUTOMASK: (tw0 + tw1 + tws) mean_p min(i_0, i_1, i_s, e_0, e_1, e_s) + tw2 mean_p min(i_2, e_2)
+ *   AUTOMASK:              every warp, the stereo one included, takes min(i_w, e_w)
+ * Ties continue the masked entry's order: identities (i_0, i_1, i_s), then reprojections (e_0, e_1, e_s); a later candidate wins only if
+ * strictly smaller.  The stereo warp has no pose gradient; its gradient goes to disp_t only.  A pixel won by an identity sends none.
+ * stereo: [B,3,H,W], the stereo frame (KITTI: image_03 for an image_02 target).
+ * stereo_baseline: [B] float on the DEVICE (read by the kernel: a captured graph honours new values without a host sync), in metres: the x
+ *   coordinate of the stereo camera's centre in the target camera's frame -- positive when the stereo camera is to the target's right
+ *   (KITTI left target, right source: +0.54), negated for a horizontally mirrored sample.
+ * term_weights: 4 floats on the HOST (tw0, tw1, tw2, tws); NULL means (1/6, 1/6, 1/2, 1/6): the target-view group is the mean of its three
+ *   warps and warp 2 keeps its half.
+ * selection: as in the masked entry; plane 0 gains code 3 = the stereo warp (codes 0, 1, 2 keep their meaning).  Without MIN_REPROJ plane 0
+ *   holds warp 0's choice; without either masked flag it is zero-filled.
+ * flags: MCAV_WL_K_F64 / SKIP_IF_UNIT / NO_SMOOTH / INPUT_DEPTH / SSIM / MIN_REPROJ / AUTOMASK.  Returns MCAV_E_INVALID for unknown flag bits
+ * or a null pointer, MCAV_E_WORKSPACE for a workspace or selection buffer that is too small. */
+int mcav_warp_loss_stereo_fwd_bwd(const float* tgt, const float* ref0, const float* ref1,
+                                  const float* disp_t, const float* disp_r0, const float* poses, const void* K,
+                                  int B, int H, int W, unsigned flags, const float* upstream, const float* term_weights,
+                                  float* losses, float* d_disp_t, float* d_disp_r0, float* d_poses,
+                                  void* workspace, size_t workspace_bytes, void* stream,
+                                  unsigned char* selection, size_t selection_bytes,
+                                  const float* stereo, const float* stereo_baseline);
+
 /* DIAGNOSTIC twin of mcav_warp_loss_fwd_bwd (upstream (1,1)): the same kernel bodies with a per-pixel dump, used by
  * tests/flip_finder.py to NAME the pixels at which an fp32 evaluation takes another bilinear cell / L1 sign than float64 does
  * (losses.py:183-240 is only piecewise smooth).  taps: [B][3 warps][7][H][W] = { ix, iy (un-normalised sampling position, source pixels),

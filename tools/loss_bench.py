@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Times the fused loss stage alone (forward call = forward + backward of the loss in ONE launch) at bench.py's shapes.
-usage: python tools/loss_bench.py [--ssim] [--min-reprojection] [--automask] [--edge-smooth] [--batch 12 --height 192 --width 640] [--iters 200]
+usage: python tools/loss_bench.py [--ssim] [--min-reprojection] [--automask] [--stereo] [--edge-smooth] [--batch 12 --height 192 --width 640] [--iters 200]
 --edge-smooth: Losses(edge_aware_smoothness=True) -- the fused kernel runs with MCAV_WL_NO_SMOOTH, and the edge-aware smoothness launches
-(mcav_edge_smooth_fwd / _bwd, scale 0) are timed per dispatch as well."""
+(mcav_edge_smooth_fwd / _bwd, scale 0) are timed per dispatch as well.
+--stereo: Losses(stereo=True) (mcav_warp_loss_stereo_fwd_bwd) with a stereo frame and baselines of +-0.54 m."""
 import argparse
 import os
 import sys
@@ -18,6 +19,7 @@ ap.add_argument("--ssim", action="store_true")
 ap.add_argument("--min-reprojection", action="store_true")
 ap.add_argument("--automask", action="store_true")
 ap.add_argument("--edge-smooth", action="store_true")
+ap.add_argument("--stereo", action="store_true")
 ap.add_argument("--batch", type=int, default=12)
 ap.add_argument("--height", type=int, default=192)
 ap.add_argument("--width", type=int, default=640)
@@ -40,24 +42,27 @@ def smooth_disp():
 
 dt, dr = smooth_disp(), smooth_disp()
 poses = (0.01 * torch.randn(B, 2, 6, generator=g)).to(dev)
-crit = Losses(ssim=a.ssim, min_reprojection=a.min_reprojection, automask=a.automask, edge_aware_smoothness=a.edge_smooth)
+crit = Losses(ssim=a.ssim, min_reprojection=a.min_reprojection, automask=a.automask, edge_aware_smoothness=a.edge_smooth, stereo=a.stereo)
+kw = {}
+if a.stereo:          # the stereo frame: the target a pixel over (a right view's order of disparity); flipped samples every other one
+    kw = dict(stereo=torch.roll(tgt, 1, dims=3).contiguous(), stereo_baseline=torch.tensor([0.54, -0.54] * B, device=dev)[:B].contiguous())
 from mcav import nn as N  # noqa: E402
 
 with torch.no_grad():
     for _ in range(20):
-        out = crit.forward(tgt, refs, [[dt], [dr]], poses, K, None)
+        out = crit.forward(tgt, refs, [[dt], [dr]], poses, K, None, **kw)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(a.iters):
-        out = crit.forward(tgt, refs, [[dt], [dr]], poses, K, None)
+        out = crit.forward(tgt, refs, [[dt], [dr]], poses, K, None, **kw)
     e1.record()
     torch.cuda.synchronize()
     call_us = 1000.0 * e0.elapsed_time(e1) / a.iters
     # the kernel's own duration: per-dispatch HIP events (csrc/kernel_timer.h), as bench.py's roofline_warp
     N.kernel_timer_begin()
     for _ in range(50):
-        out = crit.forward(tgt, refs, [[dt], [dr]], poses, K, None)
+        out = crit.forward(tgt, refs, [[dt], [dr]], poses, K, None, **kw)
     torch.cuda.synchronize()
     durs = N.kernel_timer_end()
     if a.edge_smooth:                   # a call is [fused kernel, edge-aware smoothness forward]
@@ -66,7 +71,7 @@ with torch.no_grad():
 us = 1000.0 * durs[len(durs) // 2]
 print("loss stage %s %dx%dx%d: kernel %.1f us (median of %d dispatches, min %.1f) = %.3f of the 8 TB/s HBM roofline at 52 B/pixel; %.1f us per "
       "back-to-back call incl. the host; losses %s" % (("SSIM+L1" if a.ssim else "L1") + (" min-reprojection" if a.min_reprojection else "") +
-                                                       (" automask" if a.automask else ""), B, H, W, us, len(durs), 1000.0 * durs[0],
+                                                       (" automask" if a.automask else "") + (" stereo" if a.stereo else ""), B, H, W, us, len(durs), 1000.0 * durs[0],
                                                        52.0 * B * H * W / (us * 1e-6) / 8e12, call_us, [round(float(x), 6) for x in out]))
 if a.edge_smooth:
     # the edge-aware smoothness alone: forward + backward of scale 0, one dispatch each (only the mcav launches are timed)

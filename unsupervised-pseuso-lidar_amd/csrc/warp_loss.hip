@@ -9,6 +9,7 @@
 // (wavefront shuffles -> LDS -> per-block slab -> fp64 finalize) for the 2 loss scalars and the 3x12 dP sums.
 #include <stdlib.h>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "mcav_common.h"
@@ -50,6 +51,25 @@ constexpr int WL_DBG = 7;      // ix, iy, d loss / d ix, d loss / d iy, res[0..2
 // Masked modes: the kernels' MODE template argument (0 = the plain per-warp means).  Selection codes as in include/mcav_depth.h.
 constexpr unsigned WL_M_MIN = 1u, WL_M_AUTO = 2u;
 constexpr unsigned char SEL_IDENTITY = 2;
+
+// Mono + stereo (mcav_warp_loss_stereo_fwd_bwd): a fourth warp, "s", maps the stereo frame into the target with depth(tgt), the same K and
+// the fixed transform [I | (-b, 0, 0)].  It joins pass 0 beside warps 0 and 1 and has no pose gradient.  The stereo kernels are their own
+// instantiations of the same bodies (MODE | WL_M_STEREO) with their own argument block: WLArgs and the kernels that take it are unchanged.
+constexpr unsigned WL_M_STEREO = 4u;
+constexpr unsigned char SEL_STEREO = 3;
+
+struct WLStereoArgs : WLArgs {
+    const float* stereo;           // [B,3,H,W]
+    const float* baseline;         // [B] on the device: x of the stereo camera's centre in the target camera's frame (metres)
+    float tws;                     // the stereo warp's term weight
+};
+// the stereo fields of an argument block (zero / null for WLArgs: the kernel bodies name them in code that only the stereo kernels instantiate)
+template <class A> __device__ __forceinline__ const float* stereo_frame(const A& a) {
+    if constexpr (std::is_same<A, WLStereoArgs>::value) return a.stereo; else return nullptr;
+}
+template <class A> __device__ __forceinline__ float stereo_weight(const A& a) {
+    if constexpr (std::is_same<A, WLStereoArgs>::value) return a.tws; else return 0.f;
+}
 
 __device__ __forceinline__ void load_K(const void* K, bool f64, int b, double* Kd) {
     if (f64) {
@@ -166,6 +186,11 @@ struct alignas(16) SampleFast {
     WarpFast w[3];       // 12 floats each
     float Kinv[12];      // 9 used
 };
+struct alignas(16) SampleFastStereo {
+    WarpFast w[4];       // w[3]: the stereo warp
+    float Kinv[12];
+};
+template <unsigned MODE> using SampleFastOf = std::conditional_t<(MODE & WL_M_STEREO) != 0, SampleFastStereo, SampleFast>;
 
 // Twelve wave-uniform floats from LDS as three 16-byte broadcast reads, NOT hoisted out of the pixel loop (volatile): held in registers for
 // the whole loop the three warps' constants cost 45 registers -- as scalars they overflowed the scalar file and the buffer resources with them.
@@ -194,15 +219,26 @@ __device__ __forceinline__ WarpFast lds_warp(const WarpFast& w) {
     return u;
 }
 
-__device__ __forceinline__ void block_prepare(const WLArgs& a, int b, SampleFast* sf) {
-    if (threadIdx.x < 3) {
+template <class A, class SF>
+__device__ __forceinline__ void block_prepare(const A& a, int b, SF* sf) {
+    constexpr bool ST = std::is_same<SF, SampleFastStereo>::value;
+    if (threadIdx.x < (ST ? 4 : 3)) {
         const int w = threadIdx.x;
         double Kd[9], Ki[9];
         load_K(a.K, (a.flags & MCAV_WL_K_F64) != 0, b, Kd);
         invert3x3(Kd, Ki);
         float Kf[9], Kinv[9], R[9], t[3], P[12];
         for (int i = 0; i < 9; ++i) { Kf[i] = (float)Kd[i]; Kinv[i] = (float)Ki[i]; }
-        pose_to_Rt(a.poses + (size_t)b * 12 + (w == 1 ? 6 : 0), w == 2, R, t);
+        if constexpr (ST) {
+            if (w == 3) {                                        // the stereo warp: R = I exactly, t = (-b, 0, 0), b read on the device
+                for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0f : 0.0f;
+                t[0] = -a.baseline[b]; t[1] = 0.0f; t[2] = 0.0f;
+            } else {
+                pose_to_Rt(a.poses + (size_t)b * 12 + (w == 1 ? 6 : 0), w == 2, R, t);
+            }
+        } else {
+            pose_to_Rt(a.poses + (size_t)b * 12 + (w == 1 ? 6 : 0), w == 2, R, t);
+        }
         make_P(Kf, R, t, P);
         make_fast(P, Kinv, sf->w[w]);
         if (w == 0)
@@ -327,337 +363,16 @@ constexpr int WL_STAGE = 16;      // pixels per thread between two flushes of th
 // carry the identity values in flight as well: at three workgroups per CU (168 VGPRs) they spilled, so they run at two, without scratch.
 template <bool DBG, unsigned MODE = 0>
 __global__ __launch_bounds__(256, (MODE & WL_M_AUTO) ? 2 : 3) void warp_loss_l1_kernel(WLArgs a) {
-    static_assert(!(DBG && MODE), "the per-pixel dump is a plain-mode diagnostic");
-    constexpr bool MASKED = MODE != 0, AUTO = (MODE & WL_M_AUTO) != 0, MINR = (MODE & WL_M_MIN) != 0;
-    float g0 = 1.0f, g1 = 1.0f;
-    if (a.upstream) {
-        g0 = a.upstream[0];
-        g1 = a.upstream[1];
-        if ((a.flags & MCAV_WL_SKIP_IF_UNIT) && g0 == 1.0f && g1 == 1.0f) return;
-    }
-    __shared__ SampleFast s_sf;
-    __shared__ float sD[T2LH][LW + 1];
-    __shared__ __attribute__((aligned(16))) float sred[RED_N0][RED_LD];
-    __shared__ int s_flag;
-    const int H = a.H, W = a.W, b = blockIdx.y, tid = threadIdx.x;
-    const bool pass1 = (int)blockIdx.x >= a.G0;
-    const int g = pass1 ? (int)blockIdx.x - a.G0 : (int)blockIdx.x, G = pass1 ? a.G1 : a.G0;
-    const int ntx = (W + TW - 1) / TW, nty = (H + T2H - 1) / T2H, ntiles = ntx * nty;
-    const int nmine = (ntiles - g + G - 1) / G;                  // tiles g, g + G, ... of this sample (the host keeps G <= ntiles)
-    const float inv_ntx = 1.0f / (float)ntx;
-    block_prepare(a, b, &s_sf);
+#include "warp_loss_l1_body.h"
+}
 
-    // Scalar-register budget: only the GATHERED images are buffer resources (a tap outside the image = an out-of-range offset that reads
-    // zero); the pixel-aligned reads and the gradient stores are plain global accesses under the pixel's in-image predicate.  With all seven
-    // tensors as resources plus three warps' constants the descriptors spilled into vector registers and every load became a waterfall loop.
-    const size_t plane = (size_t)H * W;
-    const int pb = (int)(plane * sizeof(float));
-    const bool in_depth = (a.flags & MCAV_WL_INPUT_DEPTH) != 0;
-    const float invN = 1.0f / (float)((size_t)a.B * 3 * plane);
-    const int tx = tid & 31, ty0 = tid >> 5;
-
-    // j-th pixel of this thread: tile j >> 1 of the workgroup's list, upper / lower half of its 16 rows
-    auto pixel = [&](int j, int& x, int& y, unsigned& off) {
-        const int t = g + (j >> 1) * G;
-        const int tyi = (int)(((float)t + 0.5f) * inv_ntx), txi = t - tyi * ntx;
-        x = txi * TW + tx;
-        y = tyi * T2H + (j & 1) * TH + ty0;
-        off = ((j >> 1) < nmine && x < W && y < H) ? (unsigned)((y * W + x) * 4) : WL_OOB;
-    };
-    auto depth_of = [&](float v) { return in_depth ? v : rcp_nr(fmaf(10.0f, v, 0.01f)); };
-    struct Set { FTap t; float q[3][4]; };
-    auto issue = [&](const WarpFast& wlds, __amdgpu_buffer_rsrc_t src, int x, int y, float D, bool live, Set& s) {
-        s.t = project_fast(lds_warp(wlds), (float)x, (float)y, D, H, W, live);
-        TapOff f;
-        const int base = (s.t.y0 * W + s.t.x0) * 4;
-        f.o[0] = s.t.in00 ? (unsigned)base : WL_OOB;
-        f.o[1] = s.t.in01 ? (unsigned)(base + 4) : WL_OOB;
-        f.o[2] = s.t.in10 ? (unsigned)(base + W * 4) : WL_OOB;
-        f.o[3] = s.t.in11 ? (unsigned)(base + W * 4 + 4) : WL_OOB;
-        gather_taps(src, f, pb, s.q);
-    };
-    auto camera_point = [&](int x, int y, float D, float* X) {
-        const F12 k = lds12(s_sf.Kinv);
-        const float fx = (float)x, fy = (float)y;
-        X[0] = fmaf(k.v[0], fx, fmaf(k.v[1], fy, k.v[2])) * D;
-        X[1] = fmaf(k.v[3], fx, fmaf(k.v[4], fy, k.v[5])) * D;
-        X[2] = fmaf(k.v[6], fx, fmaf(k.v[7], fy, k.v[8])) * D;
-    };
-    auto dump = [&](int w, unsigned off, const float* v) {
-        if (off == WL_OOB) return;
-#pragma unroll
-        for (int k = 0; k < WL_DBG; ++k) a.dbg[(((size_t)b * 3 + w) * WL_DBG + k) * plane + (off >> 2)] = v[k];
-    };
-    float acc[RED_N0];
-#pragma unroll
-    for (int k = 0; k < RED_N0; ++k) acc[k] = 0.f;
-    // d loss / d disparity of a pixel is STAGED in LDS and written out every WL_STAGE pixels.  On gfx9-family parts stores share vmcnt with
-    // loads and complete out of order with them, so with a store pending every wait for an older load becomes vmcnt(0): one global store per
-    // pixel drained the gather pipeline once per pixel (the next unit's gathers, just issued, had to land before the current unit's could be
-    // used).  Staged, that full drain happens once per 16 pixels.  The stage borrows the block reduction's scratch (used after the loop).
-    static_assert(sizeof(float) * WL_STAGE * 256 <= sizeof(float) * RED_N0 * RED_LD, "gradient stage fits the reduction scratch");
-    float* const stage = &sred[0][0];
-    static_assert(WL_STAGE * 256 * (sizeof(float) + 1) <= sizeof(float) * RED_N0 * RED_LD, "selection stage fits the reduction scratch");
-    unsigned char* const sstage = reinterpret_cast<unsigned char*>(stage + WL_STAGE * 256);      // masked modes: the pixels' selection codes
-    auto flush = [&](int j_first, int count, float* dst) {
-        for (int k = 0; k < count; ++k) {
-            int fx, fy;
-            unsigned foff;
-            pixel(j_first + k, fx, fy, foff);
-            if (foff != WL_OOB) dst[foff >> 2] = stage[k * 256 + tid];
-        }
-    };
-    auto flush_sel = [&](int j_first, int count, int pl) {      // (the optional selection map: plane 0 = warps 0 / 1, plane 1 = warp 2)
-        if (!a.sel) return;
-        unsigned char* const dst = a.sel + ((size_t)b * 2 + pl) * plane;
-        for (int k = 0; k < count; ++k) {
-            int fx, fy;
-            unsigned foff;
-            pixel(j_first + k, fx, fy, foff);
-            if (foff != WL_OOB) dst[foff >> 2] = sstage[k * 256 + tid];
-        }
-    };
-    const int npix = 2 * nmine;
-    float* const slab = a.slab + ((size_t)b * (a.G0 + a.G1) + blockIdx.x) * SLAB;
-
-    if (!pass1) {
-        // ---- pass 0: warps 0 (ref0 -> tgt) and 1 (ref1 -> tgt) with depth(tgt); the smoothness term; d loss / d disp(tgt)
-        const float gw0 = g0 * a.tw[0] * invN, gw1 = g0 * a.tw[1] * invN, lw0 = a.tw[0] * invN, lw1 = a.tw[1] * invN;
-        const float cxx = 1.0f / (float)((size_t)a.B * H * (W - 2));
-        const float cyy = 1.0f / (float)((size_t)a.B * (H - 2) * W);
-        const float cxy = 2.0f / (float)((size_t)a.B * (H - 1) * (W - 1));   // dxdy and dydx are the same field
-        const bool smooth = !(a.flags & MCAV_WL_NO_SMOOTH);
-        const WarpFast &w0 = s_sf.w[0], &w1 = s_sf.w[1];
-        const __amdgpu_buffer_rsrc_t rs_r0 = image_rsrc(a.ref0 + (size_t)b * 3 * plane, plane), rs_r1 = image_rsrc(a.ref1 + (size_t)b * 3 * plane, plane);
-        const float* const dtp = a.disp_t + (size_t)b * plane;
-        const float* const tgp = a.tgt + (size_t)b * 3 * plane;
-        float* const gtp = a.d_disp_t + (size_t)b * plane;
-        auto fetch = [&](unsigned off, float (&v)[4]) {          // disparity and the target's three channels at a pixel (zeros past the image)
-            v[0] = v[1] = v[2] = v[3] = 0.f;
-            if (off != WL_OOB) {
-                const unsigned i = off >> 2;
-                v[0] = dtp[i];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[1 + c] = tgp[c * plane + i];
-            }
-        };
-        const float* const r0p = a.ref0 + (size_t)b * 3 * plane;
-        const float* const r1p = a.ref1 + (size_t)b * 3 * plane;
-        auto fetch_src = [&](unsigned off, float (&v)[6]) {      // automask: ref0's and ref1's channels at the pixel (the identity errors)
-#pragma unroll
-            for (int c = 0; c < 6; ++c) v[c] = 0.f;
-            if (off != WL_OOB) {
-                const unsigned i = off >> 2;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { v[c] = r0p[c * plane + i]; v[3 + c] = r1p[c * plane + i]; }
-            }
-        };
-        const float lw01 = lw0 + lw1, gw01 = gw0 + gw1;         // min-reprojection: warps 0 and 1 are one term of weight tw[0] + tw[1]
-        int x, y, xn, yn;
-        unsigned off, offn;
-        float cur[4], nxt[4], idn[AUTO ? 6 : 1], i0 = 0.f, i1 = 0.f;      // automask: the current pixel's identity errors
-        auto identity = [&](const float* t) {
-            i0 = 0.f; i1 = 0.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { i0 += fabsf(idn[c] - t[c]); i1 += fabsf(idn[3 + c] - t[c]); }
-        };
-        Set s0, s1;
-        pixel(0, x, y, off);
-        fetch(off, cur);
-        if constexpr (AUTO) { fetch_src(off, idn); identity(cur + 1); }
-        float D = depth_of(cur[0]);
-        issue(w0, rs_r0, x, y, D, off != WL_OOB, s0);
-        for (int j = 0; j < npix; ++j) {
-            pixel(j + 1, xn, yn, offn);
-            fetch(offn, nxt);                                    // the next pixel's aligned values fly during this pixel's work
-            issue(w1, rs_r1, x, y, D, off != WL_OOB, s1);        // warp 1's gathers fly while warp 0 is consumed
-            float X[3], dDt = 0.f, labs = 0.f, dbg[DBG ? WL_DBG : 1];
-            camera_point(x, y, D, X);
-            float Dn;
-            if constexpr (AUTO && !MINR) {                       // automask alone: each warp against its own identity error, in the plain order
-                const float ic0 = i0, ic1 = i1;
-                fetch_src(offn, idn);                            // the next pixel's sources fly during this pixel's work
-                float e, gx, gy;
-                warp_eval_fast(s0.q, cur + 1, s0.t, e, gx, gy);
-                const float k0 = e < ic0 ? gw0 : 0.f;
-                acc[0] = fmaf(e < ic0 ? e : ic0, lw0, acc[0]);
-                sstage[(j & (WL_STAGE - 1)) * 256 + tid] = e < ic0 ? 0 : SEL_IDENTITY;      // (warp 1's choice is not stored)
-                dDt += backproject_fast(s0.t, X, gx * k0, gy * k0, H, W, acc + 2);
-                Dn = depth_of(nxt[0]);
-                issue(w0, rs_r0, xn, yn, Dn, offn != WL_OOB, s0);
-                warp_eval_fast(s1.q, cur + 1, s1.t, e, gx, gy);
-                const float k1 = e < ic1 ? gw1 : 0.f;
-                acc[0] = fmaf(e < ic1 ? e : ic1, lw1, acc[0]);
-                dDt += backproject_fast(s1.t, X, gx * k1, gy * k1, H, W, acc + 14);
-            } else if constexpr (MINR) {
-                const float ic0 = i0, ic1 = i1;
-                if constexpr (AUTO) fetch_src(offn, idn);
-                float e0, gx0, gy0, e1, gx1, gy1, dc0[3];
-                warp_eval_fast(s0.q, cur + 1, s0.t, e0, gx0, gy0);
-                const float dd0 = backproject_dc(s0.t, gx0, gy0, H, W, dc0);      // warp 0's derivative is held, unweighted, until warp 1's
-                Dn = depth_of(nxt[0]);                                            // error is known
-                issue(w0, rs_r0, xn, yn, Dn, offn != WL_OOB, s0);
-                warp_eval_fast(s1.q, cur + 1, s1.t, e1, gx1, gy1);
-                // candidates in tie order -- identities (warp 0 first), then reprojections (warp 0 first) -- a later one wins only if smaller
-                float m = e0;
-                unsigned char code = 0;
-                if constexpr (AUTO) {
-                    m = ic0;
-                    code = SEL_IDENTITY;
-                    if (ic1 < m) m = ic1;
-                    if (e0 < m) { m = e0; code = 0; }
-                }
-                if (e1 < m) { m = e1; code = 1; }
-                acc[0] = fmaf(m, lw01, acc[0]);
-                const float k0 = code == 0 ? gw01 : 0.f, k1 = code == 1 ? gw01 : 0.f;
-                apply_dc(dc0, k0, X, acc + 2);
-                dDt = fmaf(k0, dd0, dDt);
-                dDt += backproject_fast(s1.t, X, gx1 * k1, gy1 * k1, H, W, acc + 14);
-                sstage[(j & (WL_STAGE - 1)) * 256 + tid] = code;
-            } else {
-                warp_unit_fast(s0.q, cur + 1, s0.t, X, H, W, gw0, labs, dDt, acc + 2, DBG ? dbg : nullptr);
-                acc[0] = fmaf(labs, lw0, acc[0]);
-                if constexpr (DBG) dump(0, off, dbg);
-                Dn = depth_of(nxt[0]);
-                issue(w0, rs_r0, xn, yn, Dn, offn != WL_OOB, s0);    // the next pixel's warp 0 flies while warp 1 and the smoothness term are worked
-                labs = 0.f;
-                warp_unit_fast(s1.q, cur + 1, s1.t, X, H, W, gw1, labs, dDt, acc + 14, DBG ? dbg : nullptr);
-                acc[0] = fmaf(labs, lw1, acc[0]);
-                if constexpr (DBG) dump(1, off, dbg);
-            }
-            if (smooth) {
-                if (!(j & 1)) {                                  // first pixel of a tile: publish its depth tile (+ 2 halo)
-                    const int by0 = y - ty0, bx0 = x - tx;
-                    __syncthreads();                             // the previous tile's readers are done
-#pragma unroll
-                    for (int m = 0; m < 3; ++m) {
-                        const int i = tid + 256 * m, ly = i / LW, lx = i - ly * LW;
-                        const int gy = by0 - HALO + ly, gx = bx0 - HALO + lx;
-                        if (i < T2LH * LW) sD[ly][lx] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? depth_of(dtp[gy * W + gx]) : 0.f;
-                    }
-                    __syncthreads();
-                }
-                if (off != WL_OOB) {
-                    const int cy = (j & 1) * TH + ty0 + HALO, cx = tx + HALO;
-                    float gs = 0.f, ls = 0.f;
-                    smooth_terms_sel([&](int dy, int dx) { return sD[cy + dy][cx + dx]; }, x, y, H, W, cxx, cyy, cxy, ls, gs);
-                    acc[1] += ls;
-                    dDt = fmaf(g1, gs, dDt);
-                }
-            }
-            stage[(j & (WL_STAGE - 1)) * 256 + tid] = in_depth ? dDt : dDt * (-10.0f * D * D);
-            if ((j & (WL_STAGE - 1)) == WL_STAGE - 1 || j + 1 == npix) {
-                flush(j & ~(WL_STAGE - 1), (j & (WL_STAGE - 1)) + 1, gtp);
-                if constexpr (MASKED) flush_sel(j & ~(WL_STAGE - 1), (j & (WL_STAGE - 1)) + 1, 0);
-            }
-            x = xn; y = yn; off = offn; D = Dn;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
-            if constexpr (AUTO) identity(cur + 1);
-        }
-        __syncthreads();                                         // (sD and sred do not alias, but every wavefront must be out of the loop's barriers)
-        block_sum_to_slab<RED_N0>(acc, sred, slab, [](int k) { return k; });
-        if (tid >= RED_N0 && tid < SLAB) slab_store(slab + tid, 0.f);      // warp 2's slots
-    } else {
-        // ---- pass 1: warp 2 (tgt sampled with depth(ref0) and the inverted pose[0], compared with ref1: losses.py:203-207); d loss / d disp(ref0)
-        const float gw2 = g0 * a.tw[2] * invN, lw2 = a.tw[2] * invN;
-        const WarpFast& w2 = s_sf.w[2];
-        const __amdgpu_buffer_rsrc_t rs_t = image_rsrc(a.tgt + (size_t)b * 3 * plane, plane);
-        const float* const drp = a.disp_r0 + (size_t)b * plane;
-        const float* const r1p = a.ref1 + (size_t)b * 3 * plane;
-        float* const grp = a.d_disp_r0 + (size_t)b * plane;
-        auto fetch = [&](unsigned off, float (&v)[4]) {          // disparity of ref0 and ref1's three channels at a pixel (zeros past the image)
-            v[0] = v[1] = v[2] = v[3] = 0.f;
-            if (off != WL_OOB) {
-                const unsigned i = off >> 2;
-                v[0] = drp[i];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[1 + c] = r1p[c * plane + i];
-            }
-        };
-        const float* const tgp = a.tgt + (size_t)b * 3 * plane;
-        auto fetch_src = [&](unsigned off, float (&v)[3]) {      // automask: tgt's channels at the pixel (warp 2's identity error)
-            v[0] = v[1] = v[2] = 0.f;
-            if (off != WL_OOB) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) v[c] = tgp[c * plane + (off >> 2)];
-            }
-        };
-        auto identity = [&](const float* iv, const float* cv) {
-            float i2 = 0.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) i2 += fabsf(iv[c] - cv[c]);
-            return i2;
-        };
-        // automask: warp 2 at one pixel against its identity error i2 -> the selection code; loss and the kept gradient as warp_unit_fast
-        auto masked_unit = [&](const Set& s, const float* cv, float i2, const float* X, float& labs, float& dD) -> unsigned char {
-            float e, gx, gy;
-            warp_eval_fast(s.q, cv, s.t, e, gx, gy);
-            const bool keep = e < i2;
-            labs += keep ? e : i2;
-            const float k = keep ? gw2 : 0.f;
-            dD += backproject_fast(s.t, X, gx * k, gy * k, H, W, acc + 1);
-            return keep ? 0 : SEL_IDENTITY;
-        };
-        int xa, ya, xb, yb, xna, yna, xnb, ynb;
-        unsigned offa, offb, offna, offnb;
-        float ca[4], cb[4], na[4], nb[4], ina[AUTO ? 3 : 1], inb[AUTO ? 3 : 1], i2a = 0.f, i2b = 0.f;
-        Set s0, s1;
-        pixel(0, xa, ya, offa);
-        pixel(1, xb, yb, offb);
-        fetch(offa, ca);
-        fetch(offb, cb);
-        if constexpr (AUTO) {
-            fetch_src(offa, ina);
-            fetch_src(offb, inb);
-            i2a = identity(ina, ca + 1);
-            i2b = identity(inb, cb + 1);
-        }
-        float Da = depth_of(ca[0]), Db = depth_of(cb[0]);
-        issue(w2, rs_t, xa, ya, Da, offa != WL_OOB, s0);
-        for (int j = 0; j < npix; j += 2) {
-            pixel(j + 2, xna, yna, offna);
-            pixel(j + 3, xnb, ynb, offnb);
-            fetch(offna, na);
-            fetch(offnb, nb);
-            if constexpr (AUTO) { fetch_src(offna, ina); fetch_src(offnb, inb); }
-            issue(w2, rs_t, xb, yb, Db, offb != WL_OOB, s1);
-            float X[3], dDr = 0.f, labs = 0.f, dbg[DBG ? WL_DBG : 1];
-            camera_point(xa, ya, Da, X);
-            if constexpr (AUTO) sstage[(j & (WL_STAGE - 1)) * 256 + tid] = masked_unit(s0, ca + 1, i2a, X, labs, dDr);
-            else warp_unit_fast(s0.q, ca + 1, s0.t, X, H, W, gw2, labs, dDr, acc + 1, DBG ? dbg : nullptr);
-            if constexpr (MINR && !AUTO) sstage[(j & (WL_STAGE - 1)) * 256 + tid] = 0;
-            if constexpr (DBG) dump(2, offa, dbg);
-            stage[(j & (WL_STAGE - 1)) * 256 + tid] = in_depth ? dDr : dDr * (-10.0f * Da * Da);
-            const float Dna = depth_of(na[0]), Dnb = depth_of(nb[0]);
-            issue(w2, rs_t, xna, yna, Dna, offna != WL_OOB, s0);
-            dDr = 0.f;
-            camera_point(xb, yb, Db, X);
-            if constexpr (AUTO) sstage[((j + 1) & (WL_STAGE - 1)) * 256 + tid] = masked_unit(s1, cb + 1, i2b, X, labs, dDr);
-            else warp_unit_fast(s1.q, cb + 1, s1.t, X, H, W, gw2, labs, dDr, acc + 1, DBG ? dbg : nullptr);
-            if constexpr (MINR && !AUTO) sstage[((j + 1) & (WL_STAGE - 1)) * 256 + tid] = 0;
-            if constexpr (DBG) dump(2, offb, dbg);
-            stage[((j + 1) & (WL_STAGE - 1)) * 256 + tid] = in_depth ? dDr : dDr * (-10.0f * Db * Db);
-            if (((j + 1) & (WL_STAGE - 1)) == WL_STAGE - 1 || j + 2 >= npix) {
-                flush(j & ~(WL_STAGE - 1), ((j + 1) & (WL_STAGE - 1)) + 1, grp);
-                if constexpr (MASKED) flush_sel(j & ~(WL_STAGE - 1), ((j + 1) & (WL_STAGE - 1)) + 1, 1);
-            }
-            acc[0] = fmaf(labs, lw2, acc[0]);
-            xa = xna; ya = yna; offa = offna; Da = Dna;
-            xb = xnb; yb = ynb; offb = offnb; Db = Dnb;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { ca[k] = na[k]; cb[k] = nb[k]; }
-            if constexpr (AUTO) {
-                i2a = identity(ina, ca + 1);
-                i2b = identity(inb, cb + 1);
-            }
-        }
-        __syncthreads();                                         // (the stage and sred alias)
-        block_sum_to_slab<RED_N1>(acc, sred, slab, [](int k) { return k == 0 ? 0 : 25 + k; });      // loss share; dP of warp 2 -> slots 26..37
-        if (tid >= 1 && tid < 26) slab_store(slab + tid, 0.f);
-        if (tid >= 38 && tid < SLAB) slab_store(slab + tid, 0.f);
-    }
-    block_finish(a, b, a.G0 + a.G1, reinterpret_cast<double (*)[SLAB]>(&sred[0][0]), &s_flag);
+// Stereo: pass 0 holds a third warp's gathers in flight (12 floats and a tap more than the plain kernel, which already sits at 168 VGPRs
+// with three workgroups per CU): every stereo instantiation runs at two per CU, without scratch.
+template <unsigned MODE_>
+__global__ __launch_bounds__(256, 2) void warp_loss_l1_stereo_kernel(WLStereoArgs a) {
+    constexpr bool DBG = false;
+    constexpr unsigned MODE = MODE_ | WL_M_STEREO;
+#include "warp_loss_l1_body.h"
 }
 
 // ---------------------------------------------------------------------------------------------- SSIM + L1 photometric (MCAV_WL_SSIM)
@@ -707,452 +422,14 @@ constexpr int SS_N = SS_P * SS_P, SS_K = (SS_N + 255) / 256;      // statistics 
 
 template <bool DBG, unsigned MODE = 0>
 __global__ __launch_bounds__(256) void warp_loss_ssim_kernel(WLArgs a) {
-    static_assert(!(DBG && MODE), "the per-pixel dump is a plain-mode diagnostic");
-    float g0 = 1.0f, g1 = 1.0f;
-    if (a.upstream) {
-        g0 = a.upstream[0];
-        g1 = a.upstream[1];
-        if ((a.flags & MCAV_WL_SKIP_IF_UNIT) && g0 == 1.0f && g1 == 1.0f) return;
-    }
-    __shared__ float sD[WL_LH][LW + 1];
-    __shared__ float sX[3][WL_LH][LW + 1];
-    __shared__ float sT[3][WL_LH][LW + 1];
-    __shared__ __attribute__((aligned(16))) float sC[3][SS_P][SS_P + 1];
-    // LDS budget: 52.2 KB = THREE workgroups per CU.  The per-sample constants live where the block reduction's scratch will be (the
-    // reduction runs after the last use of the constants), the float64 finalize scratch on top of the coefficient fields (free by then):
-    // as separate arrays they added 2.1 KB, 163 KB for three workgroups, and the kernel ran at two per CU (0.62 -> 1.0 ms at 320x1024).
-    __shared__ __attribute__((aligned(16))) float s_red_sf[4 * SLAB];
-    float (*const sred)[SLAB] = reinterpret_cast<float (*)[SLAB]>(s_red_sf);
-    SampleFast& s_sf = *reinterpret_cast<SampleFast*>(s_red_sf);
-    static_assert(sizeof(SampleFast) <= sizeof(float) * 4 * SLAB, "constants fit the reduction scratch");
-    double (*const s64)[SLAB] = reinterpret_cast<double (*)[SLAB]>(&sC[0][0][0]);
-    static_assert(sizeof(double) * (256 / SLAB) * SLAB <= sizeof(float) * 3 * SS_P * (SS_P + 1), "finalize scratch fits the coefficient fields");
-    __shared__ int s_flag;
-    const int H = a.H, W = a.W, b = blockIdx.z;
-    const int bx0 = blockIdx.x * TW, by0 = blockIdx.y * WLH;
-    const size_t plane = (size_t)H * W;
-    const bool in_depth = (a.flags & MCAV_WL_INPUT_DEPTH) != 0;
-    const float* dt = a.disp_t + (size_t)b * plane;
-    const float* dr = a.disp_r0 + (size_t)b * plane;
-    for (int i = threadIdx.x; i < WL_LH * LW; i += 256) {
-        const int ly = i / LW, lx = i - ly * LW;
-        const int gy = by0 - HALO + ly, gx = bx0 - HALO + lx;
-        float D = 0.f;
-        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-            const float v = dt[(size_t)gy * W + gx];
-            D = in_depth ? v : rcp_nr(fmaf(10.0f, v, 0.01f));
-        }
-        sD[ly][lx] = D;
-    }
-    block_prepare(a, b, &s_sf);
-    const float* img_t = a.tgt + (size_t)b * 3 * plane;
-    const float* img_r0 = a.ref0 + (size_t)b * 3 * plane;
-    const float* img_r1 = a.ref1 + (size_t)b * 3 * plane;
-    const int tx = threadIdx.x & 31, ty0 = threadIdx.x >> 5;
-    const int x = bx0 + tx;
-    const float invN = 1.0f / (float)((size_t)a.B * 3 * plane);
-    const float WS = 0.85f, WL1 = 0.15f;              // losses.py:77
-    constexpr int NONE = -(1 << 30);
-    float acc[NACC];
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) acc[k] = 0.f;
-    float dDt[WL_SUB], dDr[WL_SUB], Dr[WL_SUB];
-#pragma unroll
-    for (int sub = 0; sub < WL_SUB; ++sub) {
-        dDt[sub] = 0.f; dDr[sub] = 0.f; Dr[sub] = 0.f;
-        const int y = by0 + sub * TH + ty0;
-        if (x < W && y < H) {
-            const float vr = dr[(size_t)y * W + x];
-            Dr[sub] = in_depth ? vr : rcp_nr(fmaf(10.0f, vr, 0.01f));
-        }
-    }
+#include "warp_loss_ssim_body.h"
+}
 
-    if constexpr (MODE != 0) {
-        constexpr bool AUTO = (MODE & WL_M_AUTO) != 0, MINR = (MODE & WL_M_MIN) != 0;
-        __shared__ unsigned char sM[WLH][TW];              // the selection code of the tile's own pixels
-        // ---- phase 1: sX <- warp w's warped source (or, ident, its unwarped source) on tile + 2 halo; sT <- its target when with_target
-        auto stage = [&](int w, bool ident, bool with_target) {
-            const float* src = w == 0 ? img_r0 : (w == 1 ? img_r1 : img_t);
-            const float* tar = w == 2 ? img_r1 : img_t;
-            const WarpFast wf = lds_warp(s_sf.w[w]);
-            for (int i = threadIdx.x; i < WL_LH * LW; i += 256) {
-                const int ly = i / LW, lx = i - ly * LW;
-                const int gy = by0 - HALO + ly, gx = bx0 - HALO + lx;
-                float xv[3] = {0.f, 0.f, 0.f}, tv[3] = {0.f, 0.f, 0.f};
-                if (gy >= -1 && gy <= H && gx >= -1 && gx <= W) {
-                    const int ry = reflect1(gy, H), rx = reflect1(gx, W);
-                    if (ident) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) xv[c] = src[c * plane + (size_t)ry * W + rx];
-                    } else {
-                        float D;
-                        if (w < 2) D = sD[ry - by0 + HALO][rx - bx0 + HALO];
-                        else {
-                            const float v = dr[(size_t)ry * W + rx];
-                            D = in_depth ? v : rcp_nr(fmaf(10.0f, v, 0.01f));
-                        }
-                        const FTap t = project_fast(wf, (float)rx, (float)ry, D, H, W);
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) {
-                            float q4[4];
-                            texels_of(src + c * plane, W, t, q4);
-                            xv[c] = bilinear_lerp(q4[0], q4[1], q4[2], q4[3], t.wx1, t.wy1).v;
-                        }
-                    }
-                    if (with_target) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) tv[c] = tar[c * plane + (size_t)ry * W + rx];
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    sX[c][ly][lx] = xv[c];
-                    if (with_target) sT[c][ly][lx] = tv[c];
-                }
-            }
-            __syncthreads();
-        };
-        // the staged candidate's error at this thread's statistics pixels (tile + 1 halo), folded into (best, code): it wins only if smaller
-        auto fold = [&](float (&best)[SS_K], unsigned& codes, unsigned code, bool first) {
-#pragma unroll
-            for (int k = 0; k < SS_K; ++k) {
-                const int i = threadIdx.x + 256 * k;
-                const int py = i / SS_P, px = i - py * SS_P;
-                const int gy = by0 - 1 + py, gx = bx0 - 1 + px;
-                float e = 0.f;
-                if (i < SS_N && gy >= 0 && gy < H && gx >= 0 && gx < W) {
-#pragma unroll 1
-                    for (int c = 0; c < 3; ++c) {
-                        float xw[9], yw[9];
-#pragma unroll
-                        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                            for (int dx = 0; dx < 3; ++dx) { xw[dy * 3 + dx] = sX[c][py + dy][px + dx]; yw[dy * 3 + dx] = sT[c][py + dy][px + dx]; }
-                        e += WS * ssim_point(xw, yw).S + WL1 * fabsf(xw[4] - yw[4]);
-                    }
-                }
-                if (first || e < best[k]) {
-                    best[k] = e;
-                    codes = (codes & ~(3u << (2 * k))) | (code << (2 * k));
-                }
-            }
-        };
-        // phases 2-4 of warp w (staged in sX) with its coefficient fields and L1 term multiplied by the selection (code `mine` of the group);
-        // single: the group has no other candidate -- every pixel is kept and the loss is accumulated here, as in the plain kernel
-        auto backward = [&](int w, unsigned codes, unsigned mine, bool single, float lw) {
-            const float* src = w == 0 ? img_r0 : (w == 1 ? img_r1 : img_t);
-            const WarpFast wf = lds_warp(s_sf.w[w]);
-            const float gw = g0 * lw;
-            float gp0[WL_SUB], gp1[WL_SUB], gp2[WL_SUB], dP[12];
-#pragma unroll
-            for (int i = 0; i < 12; ++i) dP[i] = 0.f;
-#pragma unroll 1
-            for (int c = 0; c < 3; ++c) {
-#pragma unroll
-                for (int k = 0; k < SS_K; ++k) {
-                    const int i = threadIdx.x + 256 * k;
-                    if (i >= SS_N) continue;
-                    const int py = i / SS_P, px = i - py * SS_P;
-                    const int gy = by0 - 1 + py, gx = bx0 - 1 + px;
-                    SsimPoint o;
-                    o.S = 0.f; o.a = 0.f; o.b = 0.f; o.c = 0.f;
-                    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-                        float xw[9], yw[9];
-#pragma unroll
-                        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                            for (int dx = 0; dx < 3; ++dx) { xw[dy * 3 + dx] = sX[c][py + dy][px + dx]; yw[dy * 3 + dx] = sT[c][py + dy][px + dx]; }
-                        o = ssim_point(xw, yw);
-                        if (single) {
-                            if (py >= 1 && py <= WLH && px >= 1 && px <= TW) acc[0] += lw * (WS * o.S + WL1 * fabsf(xw[4] - yw[4]));
-                        } else if (((codes >> (2 * k)) & 3u) != mine) {
-                            o.a = 0.f; o.b = 0.f; o.c = 0.f;
-                        }
-                    }
-                    sC[0][py][px] = o.a; sC[1][py][px] = o.b; sC[2][py][px] = o.c;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int sub = 0; sub < WL_SUB; ++sub) {
-                    const int ty = sub * TH + ty0, y = by0 + ty;
-                    if (c == 0) gp0[sub] = 0.f; else if (c == 1) gp1[sub] = 0.f; else gp2[sub] = 0.f;
-                    if (!(x < W && y < H)) continue;
-                    float SA = 0.f, SB = 0.f, SC = 0.f;
-#pragma unroll
-                    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                        for (int dx = 0; dx < 3; ++dx) { SA += sC[0][ty + dy][tx + dx]; SB += sC[1][ty + dy][tx + dx]; SC += sC[2][ty + dy][tx + dx]; }
-                    if (y == 1 || y == H - 2 || x == 1 || x == W - 2) {      // the reflected windows, as in the plain kernel
-                        for (int yi = 0; yi < 3; ++yi) {
-                            const int yc = yi == 0 ? y : (yi == 1 ? (y == 1 ? -1 : NONE) : (y == H - 2 ? H : NONE));
-                            if (yc == NONE) continue;
-                            for (int xi = (yi == 0 ? 1 : 0); xi < 3; ++xi) {
-                                const int xc = xi == 0 ? x : (xi == 1 ? (x == 1 ? -1 : NONE) : (x == W - 2 ? W : NONE));
-                                if (xc == NONE) continue;
-                                for (int dy = -1; dy <= 1; ++dy) {
-                                    const int qy = yc + dy;
-                                    if (qy < 0 || qy >= H) continue;
-                                    for (int dx = -1; dx <= 1; ++dx) {
-                                        const int qx = xc + dx;
-                                        if (qx < 0 || qx >= W) continue;
-                                        SA += sC[0][qy - by0 + 1][qx - bx0 + 1];
-                                        SB += sC[1][qy - by0 + 1][qx - bx0 + 1];
-                                        SC += sC[2][qy - by0 + 1][qx - bx0 + 1];
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    const float xq = sX[c][ty + HALO][tx + HALO], tq = sT[c][ty + HALO][tx + HALO];
-                    const float l1 = (single || sM[ty][tx] == mine) ? WL1 : 0.f;
-                    const float gv = gw * (l1 * sgn(xq - tq) + WS * (SA + xq * SB + tq * SC));
-                    if (c == 0) gp0[sub] = gv; else if (c == 1) gp1[sub] = gv; else gp2[sub] = gv;
-                }
-                __syncthreads();
-            }
-            // ---- phase 4: as in the plain kernel
-#pragma unroll
-            for (int sub = 0; sub < WL_SUB; ++sub) {
-                const int ty = sub * TH + ty0, y = by0 + ty;
-                if (!(x < W && y < H)) continue;
-                const float Dp = w < 2 ? sD[ty + HALO][tx + HALO] : Dr[sub];
-                const FTap t = project_fast(wf, (float)x, (float)y, Dp, H, W);
-                float gix = 0.f, giy = 0.f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float q4[4];
-                    texels_of(src + c * plane, W, t, q4);
-                    const Sample sm = bilinear_lerp(q4[0], q4[1], q4[2], q4[3], t.wx1, t.wy1);
-                    const float gv = c == 0 ? gp0[sub] : (c == 1 ? gp1[sub] : gp2[sub]);
-                    gix += gv * sm.dvdx;
-                    giy += gv * sm.dvdy;
-                }
-                const F12 k = lds12(s_sf.Kinv);
-                const float fx = (float)x, fy = (float)y;
-                const float X[3] = {fmaf(k.v[0], fx, fmaf(k.v[1], fy, k.v[2])) * Dp, fmaf(k.v[3], fx, fmaf(k.v[4], fy, k.v[5])) * Dp,
-                                    fmaf(k.v[6], fx, fmaf(k.v[7], fy, k.v[8])) * Dp};
-                const float d = backproject_fast(t, X, gix, giy, H, W, dP);
-                if (w < 2) dDt[sub] += d; else dDr[sub] += d;
-            }
-#pragma unroll
-            for (int i = 0; i < 12; ++i) {                       // (w is not a constant here: the running sums are selected, not indexed)
-                acc[2 + i] += w == 0 ? dP[i] : 0.f;
-                acc[14 + i] += w == 1 ? dP[i] : 0.f;
-                acc[26 + i] += w == 2 ? dP[i] : 0.f;
-            }
-        };
-        // one group: candidates, selection (loss, sM, the map), then the backward of every warp in it
-        auto group = [&](int wfirst, int nw, int plane_out) {
-            float lw = 0.f;
-            for (int j = 0; j < nw; ++j) lw += a.tw[wfirst + j] * invN;
-            const bool single = !AUTO && nw == 1;
-            unsigned codes = 0;
-            if (!single) {
-                float best[SS_K];
-                // candidates in tie order: the identities (AUTO), then the reprojections, warp by warp
-#pragma unroll 1
-                for (int j = 0; j < (AUTO ? 2 : 1) * nw; ++j) {
-                    const bool ident = AUTO && j < nw;
-                    const int wj = ident ? j : j - (AUTO ? nw : 0);
-                    if (j > 0) __syncthreads();                  // the previous candidate's readers are done
-                    stage(wfirst + wj, ident, j == 0);
-                    fold(best, codes, ident ? (unsigned)SEL_IDENTITY : (unsigned)wj, j == 0);
-                }
-#pragma unroll
-                for (int k = 0; k < SS_K; ++k) {
-                    const int i = threadIdx.x + 256 * k;
-                    const int py = i / SS_P, px = i - py * SS_P;
-                    if (i < SS_N && py >= 1 && py <= WLH && px >= 1 && px <= TW) {
-                        sM[py - 1][px - 1] = (unsigned char)((codes >> (2 * k)) & 3u);
-                        if (by0 - 1 + py < H && bx0 - 1 + px < W) acc[0] += lw * best[k];
-                    }
-                }
-            } else {
-                stage(wfirst, false, true);
-                for (int i = threadIdx.x; i < WLH * TW; i += 256) sM[i / TW][i % TW] = 0;
-            }
-            __syncthreads();
-            if (a.sel && plane_out < 2) {
-#pragma unroll
-                for (int sub = 0; sub < WL_SUB; ++sub) {
-                    const int ty = sub * TH + ty0, y = by0 + ty;
-                    if (x < W && y < H) a.sel[((size_t)b * 2 + plane_out) * plane + (size_t)y * W + x] = sM[ty][tx];
-                }
-            }
-#pragma unroll 1
-            for (int j = nw - 1; j >= 0; --j) {                  // the last candidate staged is the group's last warp
-                if (j != nw - 1) stage(wfirst + j, false, false);
-                backward(wfirst + j, codes, (unsigned)j, single, lw);
-            }
-            __syncthreads();                                     // sM / sX are rewritten by the next group
-        };
-        __syncthreads();                                         // sD is filled
-        // groups: min-reprojection {0, 1} -> plane 0, {2} -> plane 1; automask alone {0} -> plane 0, {1} -> not stored, {2} -> plane 1
-#pragma unroll 1
-        for (int gi = 0; gi < (MINR ? 2 : 3); ++gi) {
-            if constexpr (MINR) group(2 * gi, gi == 0 ? 2 : 1, gi);
-            else group(gi, 1, gi == 0 ? 0 : (gi == 1 ? 2 : 1));
-        }
-    } else {
-#pragma unroll
-        for (int w = 0; w < 3; ++w) {
-            const float* src = w == 0 ? img_r0 : (w == 1 ? img_r1 : img_t);
-            const float* tar = w == 2 ? img_r1 : img_t;
-            const WarpFast wf = lds_warp(s_sf.w[w]);
-            const float lw = a.tw[w] * invN, gw = g0 * lw;
-            __syncthreads();                       // sD is filled (w == 0) / the previous warp's readers are done
-            // ---- phase 1: warped and target planes on tile + 2 halo
-            for (int i = threadIdx.x; i < WL_LH * LW; i += 256) {
-                const int ly = i / LW, lx = i - ly * LW;
-                const int gy = by0 - HALO + ly, gx = bx0 - HALO + lx;
-                float xv[3] = {0.f, 0.f, 0.f}, tv[3] = {0.f, 0.f, 0.f};
-                if (gy >= -1 && gy <= H && gx >= -1 && gx <= W) {
-                    const int ry = reflect1(gy, H), rx = reflect1(gx, W);
-                    float D;
-                    if (w < 2) D = sD[ry - by0 + HALO][rx - bx0 + HALO];
-                    else {
-                        const float v = dr[(size_t)ry * W + rx];
-                        D = in_depth ? v : rcp_nr(fmaf(10.0f, v, 0.01f));
-                    }
-                    const FTap t = project_fast(wf, (float)rx, (float)ry, D, H, W);
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) {
-                        float q4[4];
-                        texels_of(src + c * plane, W, t, q4);
-                        xv[c] = bilinear_lerp(q4[0], q4[1], q4[2], q4[3], t.wx1, t.wy1).v;
-                    }
-                    if (w != 1) {
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) tv[c] = tar[c * plane + (size_t)ry * W + rx];
-                    }
-                }
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    sX[c][ly][lx] = xv[c];
-                    if (w != 1) sT[c][ly][lx] = tv[c];         // warps 0 and 1 share the target
-                }
-            }
-            __syncthreads();
-            float gp0[WL_SUB], gp1[WL_SUB], gp2[WL_SUB];        // d loss / d warped value at the thread's own pixels, per channel
-#pragma unroll 1
-            for (int c = 0; c < 3; ++c) {
-                // ---- phase 2: window statistics -> S and the gradient coefficient fields on tile + 1 halo
-                for (int i = threadIdx.x; i < SS_P * SS_P; i += 256) {
-                    const int py = i / SS_P, px = i - py * SS_P;
-                    const int gy = by0 - 1 + py, gx = bx0 - 1 + px;
-                    SsimPoint o;
-                    o.S = 0.f; o.a = 0.f; o.b = 0.f; o.c = 0.f;
-                    if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-                        float xw[9], yw[9];
-#pragma unroll
-                        for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                            for (int dx = 0; dx < 3; ++dx) { xw[dy * 3 + dx] = sX[c][py + dy][px + dx]; yw[dy * 3 + dx] = sT[c][py + dy][px + dx]; }
-                        o = ssim_point(xw, yw);
-                        if (py >= 1 && py <= WLH && px >= 1 && px <= TW) acc[0] += lw * (WS * o.S + WL1 * fabsf(xw[4] - yw[4]));
-                    }
-                    sC[0][py][px] = o.a; sC[1][py][px] = o.b; sC[2][py][px] = o.c;
-                }
-                __syncthreads();
-                // ---- phase 3: gather the coefficient fields of every window the thread's own pixels take part in
-#pragma unroll
-                for (int sub = 0; sub < WL_SUB; ++sub) {
-                    const int ty = sub * TH + ty0, y = by0 + ty;
-                    if (c == 0) gp0[sub] = 0.f; else if (c == 1) gp1[sub] = 0.f; else gp2[sub] = 0.f;
-                    if (!(x < W && y < H)) continue;
-                    float SA = 0.f, SB = 0.f, SC = 0.f;
-                    // the pixel's own 3x3 neighbourhood: always inside the statistics region, zero outside the image
-#pragma unroll
-                    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                        for (int dx = 0; dx < 3; ++dx) { SA += sC[0][ty + dy][tx + dx]; SB += sC[1][ty + dy][tx + dx]; SC += sC[2][ty + dy][tx + dx]; }
-                    if (y == 1 || y == H - 2 || x == 1 || x == W - 2) {
-                        // one pixel in from the border: the pixel is also the reflection at padded row -1 / H or column -1 / W
-                        for (int yi = 0; yi < 3; ++yi) {
-                            const int yc = yi == 0 ? y : (yi == 1 ? (y == 1 ? -1 : NONE) : (y == H - 2 ? H : NONE));
-                            if (yc == NONE) continue;
-                            for (int xi = (yi == 0 ? 1 : 0); xi < 3; ++xi) {
-                                const int xc = xi == 0 ? x : (xi == 1 ? (x == 1 ? -1 : NONE) : (x == W - 2 ? W : NONE));
-                                if (xc == NONE) continue;
-                                for (int dy = -1; dy <= 1; ++dy) {
-                                    const int qy = yc + dy;
-                                    if (qy < 0 || qy >= H) continue;
-                                    for (int dx = -1; dx <= 1; ++dx) {
-                                        const int qx = xc + dx;
-                                        if (qx < 0 || qx >= W) continue;
-                                        SA += sC[0][qy - by0 + 1][qx - bx0 + 1];
-                                        SB += sC[1][qy - by0 + 1][qx - bx0 + 1];
-                                        SC += sC[2][qy - by0 + 1][qx - bx0 + 1];
-                                    }
-                                }
-                            }
-                        }
-                    }
-                    const float xq = sX[c][ty + HALO][tx + HALO], tq = sT[c][ty + HALO][tx + HALO];
-                    const float gv = gw * (WL1 * sgn(xq - tq) + WS * (SA + xq * SB + tq * SC));
-                    if (c == 0) gp0[sub] = gv; else if (c == 1) gp1[sub] = gv; else gp2[sub] = gv;
-                }
-                __syncthreads();                   // sC is rewritten by the next channel
-            }
-            // ---- phase 4: chain through the bilinear sample to the sampling position, the depth and P
-#pragma unroll
-            for (int sub = 0; sub < WL_SUB; ++sub) {
-                const int ty = sub * TH + ty0, y = by0 + ty;
-                if (!(x < W && y < H)) continue;
-                const float Dp = w < 2 ? sD[ty + HALO][tx + HALO] : Dr[sub];
-                const FTap t = project_fast(wf, (float)x, (float)y, Dp, H, W);
-                float gix = 0.f, giy = 0.f;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float q4[4];
-                    texels_of(src + c * plane, W, t, q4);
-                    const Sample sm = bilinear_lerp(q4[0], q4[1], q4[2], q4[3], t.wx1, t.wy1);
-                    const float gv = c == 0 ? gp0[sub] : (c == 1 ? gp1[sub] : gp2[sub]);
-                    gix += gv * sm.dvdx;
-                    giy += gv * sm.dvdy;
-                }
-                const F12 k = lds12(s_sf.Kinv);
-                const float fx = (float)x, fy = (float)y;
-                const float X[3] = {fmaf(k.v[0], fx, fmaf(k.v[1], fy, k.v[2])) * Dp, fmaf(k.v[3], fx, fmaf(k.v[4], fy, k.v[5])) * Dp,
-                                    fmaf(k.v[6], fx, fmaf(k.v[7], fy, k.v[8])) * Dp};
-                const float d = backproject_fast(t, X, gix, giy, H, W, acc + 2 + 12 * w);
-                if (w < 2) dDt[sub] += d; else dDr[sub] += d;
-                if constexpr (DBG) {      // (the residual planes of the dump stay zero: the mix's value-level kinks are judged on the oracle's margins)
-                    const float v[WL_DBG] = {t.ix, t.iy, gix, giy, 0.f, 0.f, 0.f};
-#pragma unroll
-                    for (int k = 0; k < WL_DBG; ++k) a.dbg[(((size_t)b * 3 + w) * WL_DBG + k) * plane + (size_t)y * W + x] = v[k];
-                }
-            }
-        }
-    }
-
-#pragma unroll
-    for (int sub = 0; sub < WL_SUB; ++sub) {
-        const int ty = sub * TH + ty0, y = by0 + ty;
-        if (!(x < W && y < H)) continue;
-        const int cy = ty + HALO, cx = tx + HALO;
-        const size_t pix = (size_t)y * W + x;
-        const float Dt = sD[cy][cx];
-        float d = dDt[sub];
-        if (!(a.flags & MCAV_WL_NO_SMOOTH)) {
-            const float cxx = 1.0f / (float)((size_t)a.B * H * (W - 2));
-            const float cyy = 1.0f / (float)((size_t)a.B * (H - 2) * W);
-            const float cxy = 2.0f / (float)((size_t)a.B * (H - 1) * (W - 1));
-            float gs = 0.f, ls = 0.f;
-            smooth_terms([&](int dy, int dx) { return sD[cy + dy][cx + dx]; }, x, y, H, W, cxx, cyy, cxy, ls, gs);
-            acc[1] += ls;
-            d += g1 * gs;
-        }
-        a.d_disp_t[(size_t)b * plane + pix] = in_depth ? d : d * (-10.0f * Dt * Dt);
-        a.d_disp_r0[(size_t)b * plane + pix] = in_depth ? dDr[sub] : dDr[sub] * (-10.0f * Dr[sub] * Dr[sub]);
-    }
-    const int nblk = gridDim.x * gridDim.y;
-    const int blk = blockIdx.y * gridDim.x + blockIdx.x;
-    float* const slab = a.slab + ((size_t)b * nblk + blk) * SLAB;
-    __syncthreads();                                   // every reader of the constants (and of sC) is done: their LDS is re-used below
-    block_reduce_store<NACC, true>(acc, slab, sred);
-    if (threadIdx.x >= NACC && threadIdx.x < SLAB) slab_store(slab + threadIdx.x, 0.f);
-    block_finish(a, b, nblk, s64, &s_flag);
+template <unsigned MODE_>
+__global__ __launch_bounds__(256) void warp_loss_ssim_stereo_kernel(WLStereoArgs a) {
+    constexpr bool DBG = false;
+    constexpr unsigned MODE = MODE_ | WL_M_STEREO;
+#include "warp_loss_ssim_body.h"
 }
 
 // ---------------------------------------------------------------------------------------------- standalone warp
@@ -1393,27 +670,34 @@ inline WsLayout ws_layout(int B, int H, int W) {
 // workgroups per sample of the fused L1 kernel: pass 0 (warps 0, 1 + smoothness: ~2.7 units of work per tile) and pass 1 (warp 2: 1 unit), sized
 // so that every workgroup of the launch is resident at once (CUs x workgroups per CU, asked of the runtime) and the two kinds take about the
 // same time -- a second, partly filled generation would double the launch's duration
-template <unsigned MODE>
-inline int l1_slots() {
+template <auto KERNEL>
+inline int resident_slots() {
     static int slots = 0;
     if (slots == 0) {
         int dev = 0, cus = 256, per_cu = 3;
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, warp_loss_l1_kernel<false, MODE>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 3;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, KERNEL, 256, 0) != hipSuccess || per_cu < 1) per_cu = 3;
         (void)hipGetLastError();
         slots = cus * per_cu;
     }
     return slots;
 }
+template <unsigned MODE> inline int l1_slots() { return resident_slots<warp_loss_l1_kernel<false, MODE>>(); }
+template <unsigned MODE> inline int l1_stereo_slots() { return resident_slots<warp_loss_l1_stereo_kernel<MODE>>(); }
 
-inline void l1_grid(int B, int H, int W, int slots, int& G0, int& G1) {
+// stereo: a pass-0 tile gathers three warps against pass 1's one.  Measured on MI355X (tools/loss_bench.py --stereo, 12 x 192x640, L1 plain /
+// min-reprojection + automask): 1.5 -> 86.2 / 97.0 us, 2.0 -> 79.4 / 85.7, 2.7 -> 79.1 / 85.3, 3.4 -> 79.0 / 85.7, 4.0 -> 78.8 / 85.5: flat
+// from 2.0 up; 2.7 kept.  MCAV_WL_RATIO_STEREO overrides (experiments).
+inline void l1_grid(int B, int H, int W, int slots, int& G0, int& G1, bool stereo = false) {
     const int ntiles = ((W + TW - 1) / TW) * ((H + T2H - 1) / T2H);
     // tiles of a pass-1 workgroup per tile of a pass-0 workgroup.  Counted in instructions a pass-0 tile is 2.7 pass-1 tiles; measured on
     // MI355X (tools/loss_bench.py, network-like disparities, 12 x 192x640 / 12 x 320x1024): 1.0 -> 73.8 / 201 us, 2.0 -> 66.2 / 171, 2.7 -> 69.2 /
     // 172.  MCAV_WL_RATIO overrides (experiments).  Also measured and not kept: the smoothness tile's depths fetched a pixel ahead (68.4 us),
     // a three-stage pipeline with 24 .. 48 gathers in flight at two wavefronts per SIMD (68.6 .. 73 us).
-    static const float ratio = [] { const float r = MCAV_KNOB_FLOAT("MCAV_WL_RATIO", 2.0f); return r > 0.05f ? r : 2.0f; }();
+    static const float ratio_mono = [] { const float r = MCAV_KNOB_FLOAT("MCAV_WL_RATIO", 2.0f); return r > 0.05f ? r : 2.0f; }();
+    static const float ratio_stereo = [] { const float r = MCAV_KNOB_FLOAT("MCAV_WL_RATIO_STEREO", 2.7f); return r > 0.05f ? r : 2.7f; }();
+    const float ratio = stereo ? ratio_stereo : ratio_mono;
     const int per_sample = slots / B > 0 ? slots / B : 1;
     int n0 = (int)((ntiles * (1.0f + 1.0f / ratio) + per_sample - 1) / per_sample);
     if (n0 < 1) n0 = 1;
@@ -1482,11 +766,25 @@ static void launch_fused(const WLArgs& a0, hipStream_t s) {
     }
 }
 
+// one launch of the stereo kernel of (photometric term, masked mode)
+template <unsigned MODE>
+static void launch_stereo(const WLStereoArgs& a0, hipStream_t s) {
+    WLStereoArgs a = a0;
+    if (a.flags & MCAV_WL_SSIM) {
+        const dim3 wl_grid((a.W + TW - 1) / TW, (a.H + WLH - 1) / WLH, a.B);
+        timed_launch(warp_loss_ssim_stereo_kernel<MODE>, wl_grid, dim3(256), 0, s, a);
+    } else {
+        l1_grid(a.B, a.H, a.W, l1_stereo_slots<MODE>(), a.G0, a.G1, true);
+        timed_launch(warp_loss_l1_stereo_kernel<MODE>, dim3(a.G0 + a.G1, a.B), dim3(256), 0, s, a);
+    }
+}
+
+// stereo != nullptr: the stereo kernels (stereo [B,3,H,W], baseline [B] on the device, term_weights = 4 floats or nullptr)
 static int warp_loss_launch(const float* tgt, const float* ref0, const float* ref1, const float* disp_t, const float* disp_r0,
                             const float* poses, const void* K, int B, int H, int W, unsigned flags, const float* upstream,
                             const float* term_weights, float* losses, float* d_disp_t, float* d_disp_r0, float* d_poses,
                             void* workspace, size_t workspace_bytes, void* stream, float* dbg, unsigned mode = 0,
-                            unsigned char* sel = nullptr) {
+                            unsigned char* sel = nullptr, const float* stereo = nullptr, const float* baseline = nullptr) {
     if (!tgt || !ref0 || !ref1 || !disp_t || !disp_r0 || !poses || !K || !losses || !d_disp_t || !d_disp_r0 || !d_poses || !workspace)
         return MCAV_E_INVALID;
     if (B <= 0 || H < 3 || W < 3 || B > WL_MAX_B) return MCAV_E_INVALID;
@@ -1511,7 +809,21 @@ static int warp_loss_launch(const float* tgt, const float* ref0, const float* re
         mark_suspect(workspace);
         return MCAV_E_LAUNCH;
     }
-    if (mode == (WL_M_MIN | WL_M_AUTO)) launch_fused<WL_M_MIN | WL_M_AUTO>(a, s);
+    if (stereo) {
+        WLStereoArgs st;
+        static_cast<WLArgs&>(st) = a;
+        st.sel = sel;                                            // (the plain stereo kernel never writes it)
+        st.stereo = stereo;
+        st.baseline = baseline;
+        st.tw[0] = term_weights ? term_weights[0] : 1.0f / 6.0f;      // the target-view group is the mean of its three warps, warp 2 keeps half
+        st.tw[1] = term_weights ? term_weights[1] : 1.0f / 6.0f;
+        st.tw[2] = term_weights ? term_weights[2] : 0.5f;
+        st.tws = term_weights ? term_weights[3] : 1.0f / 6.0f;
+        if (mode == (WL_M_MIN | WL_M_AUTO)) launch_stereo<WL_M_MIN | WL_M_AUTO>(st, s);
+        else if (mode == WL_M_MIN) launch_stereo<WL_M_MIN>(st, s);
+        else if (mode == WL_M_AUTO) launch_stereo<WL_M_AUTO>(st, s);
+        else launch_stereo<0>(st, s);
+    } else if (mode == (WL_M_MIN | WL_M_AUTO)) launch_fused<WL_M_MIN | WL_M_AUTO>(a, s);
     else if (mode == WL_M_MIN) launch_fused<WL_M_MIN>(a, s);
     else if (mode == WL_M_AUTO) launch_fused<WL_M_AUTO>(a, s);
     else if (flags & MCAV_WL_SSIM) {
@@ -1557,6 +869,25 @@ MCAV_EXPORT int mcav_warp_loss_masked_fwd_bwd(const float* tgt, const float* ref
     }
     return warp_loss_launch(tgt, ref0, ref1, disp_t, disp_r0, poses, K, B, H, W, flags, upstream, term_weights, losses, d_disp_t, d_disp_r0,
                             d_poses, workspace, workspace_bytes, stream, nullptr, mode, selection);
+}
+
+MCAV_EXPORT int mcav_warp_loss_stereo_fwd_bwd(const float* tgt, const float* ref0, const float* ref1, const float* disp_t, const float* disp_r0,
+                                              const float* poses, const void* K, int B, int H, int W, unsigned flags, const float* upstream,
+                                              const float* term_weights, float* losses, float* d_disp_t, float* d_disp_r0, float* d_poses,
+                                              void* workspace, size_t workspace_bytes, void* stream, unsigned char* selection,
+                                              size_t selection_bytes, const float* stereo, const float* stereo_baseline) {
+    constexpr unsigned known = MCAV_WL_K_F64 | MCAV_WL_SKIP_IF_UNIT | MCAV_WL_NO_SMOOTH | MCAV_WL_INPUT_DEPTH | MCAV_WL_SSIM |
+                               MCAV_WL_MIN_REPROJ | MCAV_WL_AUTOMASK;
+    if (flags & ~known) return MCAV_E_INVALID;
+    if (!stereo || !stereo_baseline || B <= 0 || H <= 0 || W <= 0) return MCAV_E_INVALID;
+    const size_t sel_bytes = (size_t)B * 2 * H * W;
+    if (selection && selection_bytes < sel_bytes) return MCAV_E_WORKSPACE;
+    const unsigned mode = ((flags & MCAV_WL_MIN_REPROJ) ? WL_M_MIN : 0u) | ((flags & MCAV_WL_AUTOMASK) ? WL_M_AUTO : 0u);
+    const int rc = warp_loss_launch(tgt, ref0, ref1, disp_t, disp_r0, poses, K, B, H, W, flags, upstream, term_weights, losses, d_disp_t,
+                                    d_disp_r0, d_poses, workspace, workspace_bytes, stream, nullptr, mode, mode ? selection : nullptr, stereo,
+                                    stereo_baseline);
+    if (rc != MCAV_OK || mode != 0 || !selection) return rc;
+    return hipMemsetAsync(selection, 0, sel_bytes, as_stream(stream)) == hipSuccess ? MCAV_OK : MCAV_E_LAUNCH;      // plain: every warp kept
 }
 
 // Diagnostic twin of mcav_warp_loss_fwd_bwd: the same kernel bodies instantiated with their per-pixel dump on.

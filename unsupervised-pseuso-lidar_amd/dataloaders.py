@@ -256,6 +256,32 @@ def read_calib_file(path):
     return data
 
 
+def stereo_baseline_of(calib):
+    """The metric stereo baseline of a KITTI drive from its calib_cam_to_cam.txt entries (mono + stereo training, losses.Losses(stereo=True)):
+    t_i = K^-1 P_rect_0i[:, 3] (the camera's translation in the rectified frame; K = P_rect_0i[:, :3]) and b = t_2.x - t_3.x, the x of camera
+    3's centre (image_03) in camera 2's frame (image_02): ~0.533 m for 2011_09_26."""
+    t = {}
+    for i in (2, 3):
+        key = "P_rect_%02d" % i
+        if key not in calib:
+            raise ValueError("calib_cam_to_cam.txt has no %s: mono + stereo training needs both rectified projections" % key)
+        P = calib[key].reshape(3, 4)
+        t[i] = np.linalg.solve(P[:, :3], P[:, 3])
+    return float(t[2][0] - t[3][0])
+
+
+def stereo_from_config(config):
+    """loss.stereo (a bool, default off): mono + stereo training.  The dataset then also loads each target's image_03 twin and its baseline.
+    Raises ValueError, at configuration time, for a value that is not a bool or for the synthetic triplets (they have no stereo frame)."""
+    v = (config.get('loss') or {}).get('stereo', False)
+    if not isinstance(v, bool):
+        raise ValueError("config loss.stereo must be true or false, got %r" % (v,))
+    if v and config['datasets'].get('dataset', ['KITTI']) == ['synthetic']:
+        raise ValueError("config loss.stereo: mono + stereo training needs KITTI's image_03 frames and calibration; the synthetic triplets "
+                         "have no stereo frame")
+    return v
+
+
 def find_calib_dir(image_path):
     """The KITTI date directory (.../2011_09_26/) above an image path.  The reference slices a fixed number of characters off the path
     (dataloaders.py:155: [:29], 'mac - 20, beauty - 29'), which only works for its two directory layouts."""
@@ -293,8 +319,10 @@ class KittiDataset(Dataset):
         self.native_gt = gt_mode == 'native'      # the ground truth unresized, in metres (the KITTI evaluation protocol)
         self.transforms = transforms
         self.raw = transforms is None
+        self.stereo = stereo_from_config(config)     # loss.stereo: each sample also carries its target's image_03 twin and the baseline
         self.samples = []
         self._calib = {}
+        self._baseline = {}
 
     def __len__(self):
         return len(self.samples)
@@ -317,6 +345,25 @@ class KittiDataset(Dataset):
         if d not in self._calib:
             self._calib[d] = read_calib_file(d + "calib_cam_to_cam.txt")["P_rect_02"].reshape(3, 4)[:, :3].copy()
         return self._calib[d].copy()
+
+    def baseline_of(self, image_path):
+        """stereo_baseline_of the drive's calib_cam_to_cam.txt, cached per date directory."""
+        d = find_calib_dir(self.resolve(image_path))
+        if d not in self._baseline:
+            self._baseline[d] = stereo_baseline_of(read_calib_file(d + "calib_cam_to_cam.txt"))
+        return self._baseline[d]
+
+    def stereo_twin(self, image_path):
+        """The image_03 frame taken with an image_02 target.  A missing file is a configuration error, raised when the dataset is built."""
+        import os
+        parts = image_path.split("/")
+        if "image_02" not in parts:
+            raise ValueError("loss.stereo: target %r is not an image_02 frame (the stereo source is its image_03 twin)" % image_path)
+        k = len(parts) - 1 - parts[::-1].index("image_02")
+        twin = "/".join(parts[:k] + ["image_03"] + parts[k + 1:])
+        if not os.path.exists(self.resolve(twin)):
+            raise ValueError("loss.stereo: the stereo frame %s of target %s does not exist (KITTI raw: image_03 beside image_02)" % (twin, image_path))
+        return twin
 
     def load_img(self, path, gt=False):
         """-> (image, original height, original width).  raw mode: uint8 [H0, W0, 3] tensor (the GPU runs the chain); ground truth: the
@@ -352,6 +399,9 @@ class KittiDataset(Dataset):
         K[0] *= self.img_width / og_w
         K[1] *= self.img_height / og_h
         ret['intrinsics'] = torch.from_numpy(K)
+        if self.stereo:
+            ret['stereo'] = self.load_img(sample['stereo'])[0]
+            ret['stereo_baseline'] = torch.tensor(sample['stereo_baseline'], dtype=torch.float32)
         if sample.get('groundtruth'):
             ret['groundtruth'] = self.load_img(sample['groundtruth'], gt=True)[0]
         elif self.native_gt and self.raw:
@@ -375,6 +425,8 @@ class UnSupKittiFiles(KittiDataset):
                 raise ValueError("split file %s: expected 'tgt ref0 ref1 [groundtruth]', got %r" % (self.split, ln))
             self.samples.append({'tgt': parts[0], 'ref_imgs': parts[1:3], 'intrinsics': self.intrinsics_of(parts[0]),
                                  'groundtruth': parts[3] if len(parts) > 3 else None})
+            if self.stereo:
+                self.samples[-1].update(stereo=self.stereo_twin(parts[0]), stereo_baseline=self.baseline_of(parts[0]))
 
 
 def raw_collate(samples):
@@ -392,7 +444,10 @@ class PrefetchLoader:
     its bottom and right, and 'groundtruth_size' [B,2] int32 (host) holds every map's true (H, W).
     augment (an Augmentation): each batch also carries 'tgt_aug', 'ref_imgs_aug' (what the networks see) and 'augment_records' (host, one
     AUGMENT_RECORD per sample); a flipped sample's frames, ground truth (within its true size) and principal point (cx' = w - 1 - cx: the
-    warp samples pixel centres 0..w-1) are mirrored.  Call set_epoch(epoch) before each pass: the records are drawn for (seed, rank, epoch)."""
+    warp samples pixel centres 0..w-1) are mirrored.  Call set_epoch(epoch) before each pass: the records are drawn for (seed, rank, epoch).
+    Stereo samples (loss.stereo): the target's image_03 twin runs through the same plain transform as a fourth frame set (no network sees
+    it, so never jittered) -> 'stereo' [B,3,h,w], and 'stereo_baseline' [B] float32 on the device; a flipped sample's stereo frame is
+    mirrored and its baseline negated (the stereo camera is then on the other side)."""
 
     def __init__(self, loader, img_height, img_width, device="cuda", depth=2, native_groundtruth=False, augment=None):
         dev = torch.device(device)
@@ -413,24 +468,37 @@ class PrefetchLoader:
     def _finish(self, samples, stream, rng=None):
         B = len(samples)
         frames = [s['tgt'] for s in samples] + [s['ref_imgs'][0] for s in samples] + [s['ref_imgs'][1] for s in samples]
-        out = torch.empty((3 * B, 3, self.h, self.w), dtype=torch.float32, device=self.device)
+        stereo = 'stereo' in samples[0]
+        if stereo:
+            frames += [s['stereo'] for s in samples]
+        out = torch.empty((len(frames), 3, self.h, self.w), dtype=torch.float32, device=self.device)
         extra = {}
         flip = np.zeros(B, bool)
         if rng is not None:
             recs = self.augment.draw(rng, B)
             flip = (recs['flags'] & AUG_FLIP) != 0
             frame_recs = np.concatenate([recs] * 3)
-            out_aug = torch.empty_like(out)
+            out_aug = torch.empty((3 * B, 3, self.h, self.w), dtype=torch.float32, device=self.device)
             extra['augment_records'] = recs
         with torch.cuda.stream(stream):
             groups = {}
             for i, f in enumerate(frames):
                 groups.setdefault(tuple(f.shape), []).append(i)
             for shape, idx in groups.items():
-                if rng is None:
-                    out[idx] = self.transform(torch.stack([frames[i] for i in idx]))
-                else:
-                    out[idx], out_aug[idx] = self.transform.augmented(torch.stack([frames[i] for i in idx]), frame_recs[idx])
+                plain = [i for i in idx if rng is None or i >= 3 * B]      # (the stereo frames: plain transform only)
+                jitter = [i for i in idx if rng is not None and i < 3 * B]
+                if plain:
+                    out[plain] = self.transform(torch.stack([frames[i] for i in plain]))
+                if jitter:
+                    out[jitter], out_aug[jitter] = self.transform.augmented(torch.stack([frames[i] for i in jitter]), frame_recs[jitter])
+            if stereo:
+                b = torch.tensor([float(s['stereo_baseline']) for s in samples], dtype=torch.float32)
+                if flip.any():
+                    f = torch.from_numpy(flip)
+                    out[3 * B:][f.to(self.device)] = out[3 * B:][f.to(self.device)].flip(-1)
+                    b[f] = -b[f]
+                extra['stereo'] = out[3 * B:]
+                extra['stereo_baseline'] = b.pin_memory().to(self.device, non_blocking=True)
             K = torch.stack([s['intrinsics'] for s in samples])
             if flip.any():
                 f = torch.from_numpy(flip)
@@ -453,7 +521,7 @@ class PrefetchLoader:
                 gt = gt.to(self.device, non_blocking=True)
             done = torch.cuda.Event()
             done.record(stream)
-        return dict({'tgt': out[:B], 'ref_imgs': [out[B:2 * B], out[2 * B:]], 'intrinsics': K, 'groundtruth': gt}, **extra), done
+        return dict({'tgt': out[:B], 'ref_imgs': [out[B:2 * B], out[2 * B:3 * B]], 'intrinsics': K, 'groundtruth': gt}, **extra), done
 
     def __iter__(self):
         import queue
@@ -482,7 +550,8 @@ class PrefetchLoader:
             batch, done = item
             torch.cuda.current_stream(self.device).wait_event(done)
             for v in [batch['tgt']] + batch['ref_imgs'] + [batch['intrinsics'], batch['groundtruth']] + \
-                    ([batch['tgt_aug']] + batch['ref_imgs_aug'] if 'tgt_aug' in batch else []):
+                    ([batch['tgt_aug']] + batch['ref_imgs_aug'] if 'tgt_aug' in batch else []) + \
+                    ([batch['stereo'], batch['stereo_baseline']] if 'stereo' in batch else []):
                 v.record_stream(torch.cuda.current_stream(self.device))
             yield batch
         t.join()
@@ -493,6 +562,7 @@ def UnSupKittiDataset(config, transforms=None):
     offline); anything else -> the split-file driven KITTI reader above.  A missing split file or data root fails HERE, at configuration
     time, with the path in the message."""
     import os
+    stereo_from_config(config)                   # (loss.stereo with the synthetic triplets fails here)
     if config['datasets'].get('dataset', ['KITTI']) == ['synthetic']:
         return SyntheticTriplets(config, transforms)
     split = config['datasets']['split']

@@ -18,10 +18,15 @@ from mcav import lib as L
 
 class _WarpLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, disp_t, disp_r, poses, tgt, ref0, ref1, K, flags, term_weights, selection=None):
+    def forward(ctx, disp_t, disp_r, poses, tgt, ref0, ref1, K, flags, term_weights, selection=None, stereo=None, baseline=None):
         B, _, H, W = tgt.shape
         for n, t in (("tgt", tgt), ("ref0", ref0), ("ref1", ref1), ("disp_t", disp_t), ("disp_r", disp_r), ("poses", poses)):
             L.dev(t, n)
+        if stereo is not None:              # mono + stereo: the fixed-baseline fourth warp (include/mcav_depth.h: mcav_warp_loss_stereo_fwd_bwd)
+            L.dev(stereo, "stereo")
+            L.dev(baseline, "stereo_baseline")
+            if stereo.shape != tgt.shape or baseline.numel() != B or len(term_weights) != 4:
+                raise L.MCAVError("stereo: the frame must be [B,3,H,W] like tgt, stereo_baseline [B], and there are 4 term weights")
         if K.dtype == torch.float64:
             flags |= L.WL_K_F64
         L.dev(K, "intrinsics", K.dtype)
@@ -31,27 +36,32 @@ class _WarpLossFn(torch.autograd.Function):
         g_dt = torch.empty_like(disp_t)
         g_dr = torch.empty_like(disp_r)
         g_p = torch.empty_like(poses)
-        tw = (ctypes.c_float * 3)(*term_weights)
+        tw = (ctypes.c_float * len(term_weights))(*term_weights)
         args = [L.ptr(tgt), L.ptr(ref0), L.ptr(ref1), L.ptr(disp_t), L.ptr(disp_r), L.ptr(poses), L.ptr(K), B, H, W]
         tail = [tw, L.ptr(losses), L.ptr(g_dt), L.ptr(g_dr), L.ptr(g_p), L.ptr(ws), ws.numel(), L.stream()]
         from mcav import nn as N
         i0 = h.mcav_kernel_timer_count() if N.PROFILE_LOSS is not None else 0
         masked = (flags & (L.WL_MIN_REPROJ | L.WL_AUTOMASK)) != 0
-        if masked:          # min-reprojection / auto-masking: the same kernels' masked instantiations (include/mcav_depth.h)
+        if stereo is not None:
+            sel = [L.ptr(selection), selection.numel() if selection is not None else 0]
+            L.check(h.mcav_warp_loss_stereo_fwd_bwd(*args, flags, None, *tail, *sel, L.ptr(stereo), L.ptr(baseline)),
+                    "mcav_warp_loss_stereo_fwd_bwd")
+        elif masked:        # min-reprojection / auto-masking: the same kernels' masked instantiations (include/mcav_depth.h)
             sel = [L.ptr(selection), selection.numel() if selection is not None else 0]
             L.check(h.mcav_warp_loss_masked_fwd_bwd(*args, flags, None, *tail, *sel), "mcav_warp_loss_masked_fwd_bwd")
         else:
             L.check(h.mcav_warp_loss_fwd_bwd(*args, flags, None, *tail), "mcav_warp_loss_fwd_bwd")
         if N.PROFILE_LOSS is not None:
             N.PROFILE_LOSS.append(("warp_loss", i0, h.mcav_kernel_timer_count()))       # ONE launch since round 3 (prepare / finalize folded in)
-        ctx.rerun = (args, tail, flags, (tgt, ref0, ref1, disp_t, disp_r, poses, K, ws, losses))
+        st = None if stereo is None else [L.ptr(stereo), L.ptr(baseline)]
+        ctx.rerun = (args, tail, flags, st, (tgt, ref0, ref1, disp_t, disp_r, poses, K, ws, losses, stereo, baseline))
         ctx.grads = (g_dt, g_dr, g_p)
         l0, l1 = losses.unbind(0)
         return l0, l1
 
     @staticmethod
     def backward(ctx, g0, g1):
-        args, tail, flags, keep = ctx.rerun
+        args, tail, flags, st, keep = ctx.rerun
         g_dt, g_dr, g_p = ctx.grads
         dev = g_dt.device
         if g0 is not None and g1 is not None:          # the usual case (sum(loss).backward()): ONE launch instead of a fill and two copies
@@ -66,12 +76,18 @@ class _WarpLossFn(torch.autograd.Function):
         tail = list(tail)
         tail[1] = L.ptr(scratch)        # loss values are not needed again
         # no-op on the device when upstream == (1, 1); otherwise recomputes the gradients with the real weights
-        if flags & (L.WL_MIN_REPROJ | L.WL_AUTOMASK):      # (the re-run selects exactly as the first run did: same inputs, same code)
+        if st is not None:                                 # (as the masked entry: the re-run selects exactly as the first run did)
+            L.check(L.lib().mcav_warp_loss_stereo_fwd_bwd(*args, flags | L.WL_SKIP_IF_UNIT, L.ptr(up), *tail, L.ptr(None), 0, *st),
+                    "mcav_warp_loss_stereo_fwd_bwd(bwd)")
+        elif flags & (L.WL_MIN_REPROJ | L.WL_AUTOMASK):      # (the re-run selects exactly as the first run did: same inputs, same code)
             L.check(L.lib().mcav_warp_loss_masked_fwd_bwd(*args, flags | L.WL_SKIP_IF_UNIT, L.ptr(up), *tail, L.ptr(None), 0),
                     "mcav_warp_loss_masked_fwd_bwd(bwd)")
         else:
             L.check(L.lib().mcav_warp_loss_fwd_bwd(*args, flags | L.WL_SKIP_IF_UNIT, L.ptr(up), *tail), "mcav_warp_loss_fwd_bwd(bwd)")
-        return g_dt, g_dr, g_p, None, None, None, None, None, None, None
+        return g_dt, g_dr, g_p, None, None, None, None, None, None, None, None, None
+
+
+STEREO_TERM_WEIGHTS = (1 / 6, 1 / 6, 0.5, 1 / 6)      # (tw0, tw1, tw2, tws): the target-view group is the mean of its three warps
 
 
 class SSIM:
@@ -104,11 +120,20 @@ class Losses:
     `edge_aware_smoothness` (attribute as well; trainer config `loss: {edge_aware_smoothness: true, edge_smoothness_weight: 1e-3}`) replaces
     the reference's second-order depth smoothness with monodepth2's term, `edge_aware_smooth_loss(disparities of tgt, tgt)`: first order, on
     disparity divided by its per-image mean, weighted down at image edges, `edge_smoothness_weight` (1e-3) / n_scales * 2^-s per scale
-    (include/mcav_depth.h: mcav_edge_smooth_fwd).  loss_mam is what the same call gives without it."""
+    (include/mcav_depth.h: mcav_edge_smooth_fwd).  loss_mam is what the same call gives without it.
+
+    `stereo` (attribute as well; trainer config `loss: {stereo: true}`) is monodepth2's mono + stereo training: `forward(...,
+    stereo=<[B,3,H,W] stereo frame of the target>, stereo_baseline=<[B] float32, metres>)` adds that frame as one more source view of the
+    target, warped with depth(tgt) and the FIXED transform [I | (-b, 0, 0)] (include/mcav_depth.h: mcav_warp_loss_stereo_fwd_bwd).  It
+    joins warps 0 and 1 -- in their per-pixel minimum under `min_reprojection`, with its own identity error under `automask` -- and its known
+    metric baseline makes the learnt depth metric: what pseudo-LiDAR needs.  Term weights (1/6, 1/6, 1/6 and 1/2 for warp 2) / n_scales;
+    selection code 3 = the stereo warp.  b is the x of the stereo camera's centre in the target camera's frame (KITTI left target: +0.54),
+    negated for a mirrored sample."""
 
     def __init__(self, ssim=False, min_reprojection=False, automask=False, keep_selection=False, edge_aware_smoothness=False,
-                 edge_smoothness_weight=1e-3):
+                 edge_smoothness_weight=1e-3, stereo=False):
         self.clip_loss = 0.5
+        self.stereo = bool(stereo)
         self.ssim = bool(ssim)
         self.min_reprojection = bool(min_reprojection)
         self.automask = bool(automask)
@@ -130,8 +155,24 @@ class Losses:
         alloc = torch.empty if self._mask_flags() else torch.zeros      # (the plain loss keeps every warp: all zeros)
         return alloc((B, 2, H, W), dtype=torch.uint8, device=tgt.device)
 
-    def forward(self, tgt_img, ref_imgs, disparity, poses, intrinsics, gt=None):
-        """-> [loss_mam, loss_smooth].  disparity = [disps(tgt), disps(ref0)], each a list over scales."""
+    def _stereo_inputs(self, tgt_img, stereo, stereo_baseline):
+        if not self.stereo:
+            if stereo is not None or stereo_baseline is not None:
+                raise L.MCAVError("stereo / stereo_baseline given to a Losses without .stereo: set Losses(stereo=True) (trainer config "
+                                  "`loss: {stereo: true}`) for mono + stereo training, or pass neither")
+            return None, None
+        if stereo is None or stereo_baseline is None:
+            raise L.MCAVError("Losses(stereo=True) needs the stereo frame and stereo_baseline (forward(..., stereo=, stereo_baseline=))")
+        b = stereo_baseline
+        if not torch.is_tensor(b):
+            b = torch.as_tensor(b, dtype=torch.float32)
+        b = b.to(device=tgt_img.device, dtype=torch.float32).reshape(-1).contiguous()
+        return stereo.contiguous(), b
+
+    def forward(self, tgt_img, ref_imgs, disparity, poses, intrinsics, gt=None, stereo=None, stereo_baseline=None):
+        """-> [loss_mam, loss_smooth].  disparity = [disps(tgt), disps(ref0)], each a list over scales.  stereo / stereo_baseline: the
+        stereo frame [B,3,H,W] and its baseline [B] (metres), used (and required) when `.stereo` is set."""
+        st, sb = self._stereo_inputs(tgt_img, stereo, stereo_baseline)
         disp_t, disp_r = disparity[0], disparity[1]
         n = len(disp_t)
         ssim_flag = self._flags(max(n, len(disp_r)))
@@ -141,16 +182,18 @@ class Losses:
             sel = [] if self.keep_selection else None
             out = multiscale_losses(tgt_img, ref_imgs, disparity, poses, intrinsics, ssim=self.ssim, min_reprojection=self.min_reprojection,
                                     automask=self.automask, selections=sel, edge_aware_smoothness=self.edge_aware_smoothness,
-                                    edge_smoothness_weight=self.edge_smoothness_weight)
+                                    edge_smoothness_weight=self.edge_smoothness_weight, stereo=st, stereo_baseline=sb)
             if sel is not None:
                 self.selection = sel
             return out
         tw = (0.25, 0.25, 0.5)     # mean of the two tgt-view L1 terms and the third term, averaged (losses.py:227-240)
+        if st is not None:
+            tw = STEREO_TERM_WEIGHTS
         sel = self._selection(tgt_img)
         smooth_flag = L.WL_NO_SMOOTH if self.edge_aware_smoothness else 0
         l0, l1 = _WarpLossFn.apply(disp_t[0].contiguous(), disp_r[0].contiguous(), poses.contiguous(), tgt_img.contiguous(),
                                    ref_imgs[0].contiguous(), ref_imgs[1].contiguous(), intrinsics.contiguous(),
-                                   ssim_flag | mask_flags | smooth_flag, tw, sel)
+                                   ssim_flag | mask_flags | smooth_flag, tw, sel, st, sb)
         if sel is not None:
             self.selection = [sel]
         if self.edge_aware_smoothness:

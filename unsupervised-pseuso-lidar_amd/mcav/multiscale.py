@@ -131,13 +131,14 @@ class _ResizeFn(torch.autograd.Function):
 
 
 def multiscale_losses(tgt, refs, disparity, poses, K, inputs_are_depth=False, ssim=False, min_reprojection=False, automask=False,
-                      selections=None, edge_aware_smoothness=False, edge_smoothness_weight=1e-3):
+                      selections=None, edge_aware_smoothness=False, edge_smoothness_weight=1e-3, stereo=None, stereo_baseline=None):
     """Losses.forward for depth nets that return several scales (DispNetS).  Per scale: depth (from disparity), bilinear resize
     to the image size, the fused 3-warp kernel (L1, or the 0.85 SSIM + 0.15 L1 mix when ssim: the reference composes its photometric
     term per scale, losses.py:209-221) on the resized depths; smoothness on the native-resolution depths of tgt.
     min_reprojection / automask: the masked modes of losses.Losses, applied per scale; selections: a list that receives each scale's
     selection map (uint8 [B,2,H,W]).  edge_aware_smoothness: the smoothness term is edge_smooth_loss(disparities of tgt, tgt,
-    edge_smoothness_weight) instead (disparity inputs only)."""
+    edge_smoothness_weight) instead (disparity inputs only).  stereo / stereo_baseline: the mono + stereo loss at every scale (the stereo
+    frame [B,3,H,W], its baseline [B] float32 on the device; term weights (1/6, 1/6, 1/2, 1/6) / n)."""
     import losses as LS                      # the fused kernel's autograd node
     from geometry.pose_geometry import disp_to_depth
     from mcav import tape  # noqa: F401  (registers the resize entry points)
@@ -145,6 +146,9 @@ def multiscale_losses(tgt, refs, disparity, poses, K, inputs_are_depth=False, ss
     n = len(depths[0])
     H, W = tgt.shape[-2:]
     tw = (0.5 / (2 * n), 0.5 / (2 * n), 1.0 / (2 * n))      # mean of the two tgt-view terms; every term / (2 n)  (losses.py:227-240)
+    if stereo is not None:
+        tw = tuple(w / n for w in LS.STEREO_TERM_WEIGHTS)
+        stereo, stereo_baseline = stereo.contiguous(), stereo_baseline.contiguous()
     flags = L.WL_INPUT_DEPTH | L.WL_NO_SMOOTH | (L.WL_SSIM if ssim else 0)
     flags |= (L.WL_MIN_REPROJ if min_reprojection else 0) | (L.WL_AUTOMASK if automask else 0)
     masked = min_reprojection or automask
@@ -158,7 +162,7 @@ def multiscale_losses(tgt, refs, disparity, poses, K, inputs_are_depth=False, ss
             sel = (torch.empty if masked else torch.zeros)((tgt.shape[0], 2, H, W), dtype=torch.uint8, device=tgt.device)
             selections.append(sel)
         l0, _ = LS._WarpLossFn.apply(Dt.contiguous(), Dr.contiguous(), poses.contiguous(), tgt.contiguous(), refs[0].contiguous(),
-                                     refs[1].contiguous(), K.contiguous(), flags, tw, sel)
+                                     refs[1].contiguous(), K.contiguous(), flags, tw, sel, stereo, stereo_baseline)
         total = l0 if total is None else total + l0
     if edge_aware_smoothness:
         if inputs_are_depth:

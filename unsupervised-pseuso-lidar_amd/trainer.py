@@ -78,6 +78,8 @@ class Trainer:
         self.criterion.automask = bool((config.get('loss') or {}).get('automask', False))                   # and identity auto-masking
         self.criterion.edge_aware_smoothness = bool((config.get('loss') or {}).get('edge_aware_smoothness', False))   # monodepth2's smoothness
         self.criterion.edge_smoothness_weight = float((config.get('loss') or {}).get('edge_smoothness_weight', 1e-3))
+        from dataloaders import stereo_from_config
+        self.criterion.stereo = stereo_from_config(config)      # opt-in mono + stereo (metric depth): batches carry 'stereo' / 'stereo_baseline'
         self.validation = self.validation_config(config.get('validation'))      # opt-in KITTI protocol for validate()
         from mcav.streams import Branch
         self.pose_branch = Branch()
@@ -182,21 +184,27 @@ class Trainer:
         K = samples['intrinsics'].to(dev, non_blocking=True)
         aug = [samples['tgt_aug']] + list(samples['ref_imgs_aug']) if 'tgt_aug' in samples else []
         aug = [img.to(dev, non_blocking=True) for img in aug]          # augmentation: the networks' inputs, three more graph inputs
+        st = [samples['stereo'], samples['stereo_baseline']] if 'stereo' in samples else []
+        st = [t.to(dev, non_blocking=True) for t in st]                # mono + stereo: the frame and the baselines, two more graph inputs
         if self._graphs is None:
             from mcav.graph import StepGraphs
+            naug = len(aug)
 
-            def fwd_bwd(tgt, ref0, ref1, K, *aug):
+            def fwd_bwd(tgt, ref0, ref1, K, *extra):
                 self.model_optimizer.zero_grad()
+                aug, st = extra[:naug], extra[naug:]
                 batch = {'tgt': tgt, 'ref_imgs': [ref0, ref1], 'intrinsics': K, 'groundtruth': None}
                 if aug:
                     batch.update(tgt_aug=aug[0], ref_imgs_aug=[aug[1], aug[2]])
+                if st:
+                    batch.update(stereo=st[0], stereo_baseline=st[1])
                 _, loss = self.process_batch(batch)
                 sum(loss).backward()
                 return tuple(loss)
             buffers = list(self.depth_model.buffers()) + list(self.pose_model.buffers())
             self._graphs = StepGraphs(fwd_bwd, self.model_optimizer, capture_adam=not mdist.parallel(), buffers=buffers)
         self.model_optimizer.grad_scale = 1.0 / self.world
-        self.loss = list(self._graphs(tgt, ref_imgs[0], ref_imgs[1], K, *aug))
+        self.loss = list(self._graphs(tgt, ref_imgs[0], ref_imgs[1], K, *aug, *st))
         if mdist.parallel():      # the buckets' collectives are already in flight behind the replaying graph (mcav/graph.py); remainder, wait, Adam
             self.model_optimizer.grad_scale = mdist.allreduce_gradients(self.model_optimizer.arena())
             self.model_optimizer.step()
@@ -270,7 +278,10 @@ class Trainer:
             poses = self.pose_model(net_tgt, net_refs)
         if warp_test:
             return [disps, poses]
-        loss = self.criterion.forward(tgt, ref_imgs, disps, poses, intrinsics, gt)
+        st = {}
+        if 'stereo' in samples:       # mono + stereo (loss.stereo): the target's stereo frame and its baseline join the loss only
+            st = dict(stereo=samples['stereo'].to(dev, non_blocking=True), stereo_baseline=samples['stereo_baseline'].to(dev, non_blocking=True))
+        loss = self.criterion.forward(tgt, ref_imgs, disps, poses, intrinsics, gt, **st)
         return [disps, poses], loss
 
     VALIDATION_DEFAULTS = {'protocol': 'eigen', 'crop': 'garg', 'min_depth': 1e-3, 'max_depth': 80.0, 'median_scaling': True, 'scale': 1.0}
