@@ -231,6 +231,34 @@ int mcav_pseudo_lidar_project(const float* depth, int rows, int cols, const doub
                               double* cloud, size_t capacity_points, unsigned* count_out_dev, void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* KITTI Eigen ground truth from raw Velodyne scans (monodepth2 kitti_utils.generate_depth_map), the forward direction of the projection
+ * above: scan -> sparse depth map, per image of a batch.  The definition is tests/velo_ref.py; for image b with points p = (x, y, z, r)
+ * (float32, as stored in the .bin file; r is never read), P = P[b] (3x4 velodyne -> image, float64) and true size (Hb, Wb) = sizes[b]:
+ *   keep          x >= 0 in float32 (NaN fails, -0.0 passes)
+ *   project       q_k = ((P[k,0] x + P[k,1] y) + P[k,2] z) + P[k,3], k = 0, 1, 2: float64, x, y, z widened exactly, every operation
+ *                 rounded on its own (no FMA), in this order
+ *   pixel         u = rint(q0 / q2) - 1, v = rint(q1 / q2) - 1: IEEE float64 division, round half to even (np.round; not C's round())
+ *   land          u >= 0 && v >= 0 && u < Wb && v < Hb, compared in float64 (NaN and +-inf fail), converted to int only then
+ *   depth         d = q2; with MCAV_VELO_DEPTH_FROM_X (monodepth2's vel_depth=True) d = (double)x
+ *   out[b][v][u'] = float32 of the minimum d over the points that land on that pixel, u' = Wb - 1 - u when flip[b] != 0, else u;
+ *                 +0.0 where no point lands and where that minimum has its float32 sign bit set (monodepth2's depth[depth < 0] = 0:
+ *                 points with 0 <= x < ~0.27 m lie behind the camera and can land with q2 < 0); +inf (a depth above FLT_MAX) is kept.
+ *   [Hb, Hg) x [0, Wg) and [0, Hb) x [Wb, Wg) are 0: out is the zero-padded [B, Hg, Wg] map that mcav_eval_depth takes with sizes.
+ * Differences from monodepth2: its duplicate resolution (sub2ind = row * (W - 1) + col - 1) aliases pixel (r, W-1) with (r+1, 0), so on
+ * columns 0 and W-1 its result depends on the order of the points; this is the plain per-pixel minimum everywhere.  The Garg and Eigen crops
+ * exclude both columns.  monodepth2 forms P p with np.dot (a BLAS order), which can differ from the fixed order above by one float64 ulp.
+ * points: device [N,4] float32, the scans concatenated as read; offsets: device [B+1], image b owns points [offsets[b], offsets[b+1]);
+ * P: device [B,12] row-major; sizes: device int [B,2] (Hb, Wb); flip: device [B] or NULL (no flips); out: device [B,Hg,Wg] float32.
+ * max_points bounds the grid: each image's range is clamped to max_points points and sizes to [0, Hg] x [0, Wg] in the kernel, so no value
+ * reads or writes out of bounds (offsets must lie inside points).  out holds the minima as order-preserving keys while the call runs (integer
+ * atomicMin, no workspace): the map is bit-identical from run to run and for any order of the points within a scan.  No host
+ * synchronisation, allocation or copy: the call can be captured in a hipGraph.  3 launches (init, scatter, finalize).
+ * Returns MCAV_E_INVALID for a null required pointer, B, Hg or Wg <= 0, B > 65535, B * Hg * Wg * 4 >= 2^62, max_points < 0 or unknown flag
+ * bits; nothing is launched then. */
+#define MCAV_VELO_DEPTH_FROM_X 1
+int mcav_velo_depth_map(const float* points, const long long* offsets, const double* P, const int* sizes, const unsigned char* flip,
+                        int B, int Hg, int Wg, long long max_points, int flags, float* out, void* stream);
+
 /* ---- before the training step ------------------------------------------------------------------------ */
 
 /* The reference's image transform chain (dataloaders.py:32-49 load_img, trainer.py:97-103): decoded uint8 RGB -> /255 -> ToTensor ->

@@ -8,6 +8,8 @@ training step consumes is kept: a dict with 'tgt' [3,H,W], 'ref_imgs' [2 x [3,H,
 'groundtruth' [1,H,W] (reference dataloaders.py:226-251).  SyntheticTriplets produces such samples from a seed.
 `datasets.groundtruth: native` (opt-in, for evaluate.evaluate_depth): the ground truth stays at its own size, in metres, and PrefetchLoader
 zero-pads each batch to its largest map and adds 'groundtruth_size' [B,2] int32 (host).  The loss never reads the ground truth.
+`datasets.groundtruth: velodyne` (opt-in): the same native layout, but each map is made on the GPU from the frame's raw Velodyne scan
+(<drive>/velodyne_points/data/<frame>.bin), as monodepth2's Eigen-split ground truth (geometry.velodyne.depth_maps).
 `datasets.augmentation.color_jitter` / `.flip` (opt-in, Augmentation): monodepth2's training-time colour jitter and horizontal flip, on the
 GPU with the resize; the training batches then also carry 'tgt_aug', 'ref_imgs_aug' (what the networks see) and 'augment_records'.
 """
@@ -16,6 +18,8 @@ import ctypes
 import numpy as np
 import torch
 from torch.utils.data import Dataset
+
+from geometry import velodyne
 
 
 class GpuImageTransform:
@@ -314,15 +318,20 @@ class KittiDataset(Dataset):
         self.img_height = ds['augmentation']['image_height']
         self.seq_len = ds.get('sequence_length', 3)
         gt_mode = ds.get('groundtruth', 'resized')
-        if gt_mode not in ('resized', 'native'):
-            raise ValueError("datasets.groundtruth must be 'resized' (default) or 'native', got %r" % (gt_mode,))
-        self.native_gt = gt_mode == 'native'      # the ground truth unresized, in metres (the KITTI evaluation protocol)
+        if gt_mode not in ('resized', 'native', 'velodyne'):
+            raise ValueError("datasets.groundtruth must be 'resized' (default), 'native' or 'velodyne', got %r" % (gt_mode,))
+        # the ground truth unresized, in metres (the KITTI evaluation protocol); velodyne: projected from the raw scans on the GPU
+        self.native_gt = gt_mode in ('native', 'velodyne')
+        self.velodyne_gt = gt_mode == 'velodyne'
         self.transforms = transforms
         self.raw = transforms is None
+        if self.velodyne_gt and not self.raw:
+            raise ValueError("datasets.groundtruth: velodyne builds the maps on the GPU (PrefetchLoader); it takes no host transforms")
         self.stereo = stereo_from_config(config)     # loss.stereo: each sample also carries its target's image_03 twin and the baseline
         self.samples = []
         self._calib = {}
         self._baseline = {}
+        self._velo = {}
 
     def __len__(self):
         return len(self.samples)
@@ -365,6 +374,31 @@ class KittiDataset(Dataset):
             raise ValueError("loss.stereo: the stereo frame %s of target %s does not exist (KITTI raw: image_03 beside image_02)" % (twin, image_path))
         return twin
 
+    def velodyne_scan(self, image_path, override=None):
+        """The raw scan of an image_02 frame: <drive>/velodyne_points/data/<frame>.bin, or `override` (a split file's 4th column ending in
+        .bin).  A missing file is a configuration error, raised when the dataset is built."""
+        import os
+        scan = override
+        if scan is None:
+            parts = image_path.split("/")
+            if "image_02" not in parts:
+                raise ValueError("datasets.groundtruth: velodyne: target %r is not an image_02 frame (KITTI raw: velodyne_points beside "
+                                 "image_02)" % image_path)
+            k = len(parts) - 1 - parts[::-1].index("image_02")
+            scan = os.path.splitext("/".join(parts[:k] + ["velodyne_points"] + parts[k + 1:]))[0] + ".bin"
+        if not os.path.exists(self.resolve(scan)):
+            raise ValueError("datasets.groundtruth: velodyne: the scan %s of target %s does not exist (KITTI raw: "
+                             "velodyne_points/data/<frame>.bin beside image_02)" % (scan, image_path))
+        return scan
+
+    def velo_calib_of(self, image_path):
+        """geometry.velodyne.velo_to_image of the drive's date directory -> (P [3,4] float64, (H, W)), cached per directory."""
+        d = find_calib_dir(self.resolve(image_path))
+        if d not in self._velo:
+            self._velo[d] = velodyne.velo_to_image(d, 2)
+        P, hw = self._velo[d]
+        return P.copy(), hw
+
     def load_img(self, path, gt=False):
         """-> (image, original height, original width).  raw mode: uint8 [H0, W0, 3] tensor (the GPU runs the chain); ground truth: the
         depth PNG as float32, resized with Pillow's bilinear filter on mode 'F' (what ToPILImage + Resize do to a float map), [1, h, w];
@@ -402,7 +436,16 @@ class KittiDataset(Dataset):
         if self.stereo:
             ret['stereo'] = self.load_img(sample['stereo'])[0]
             ret['stereo_baseline'] = torch.tensor(sample['stereo_baseline'], dtype=torch.float32)
-        if sample.get('groundtruth'):
+        if self.velodyne_gt:
+            # the raw scan, unfiltered: PrefetchLoader projects the batch's scans on the GPU
+            if tuple(sample['velodyne_size']) != (og_h, og_w):
+                raise ValueError("datasets.groundtruth: velodyne: S_rect_02 of %s gives %dx%d, the decoded target %s is %dx%d" %
+                                 (find_calib_dir(self.resolve(sample['tgt'])), sample['velodyne_size'][0], sample['velodyne_size'][1],
+                                  sample['tgt'], og_h, og_w))
+            ret['velodyne'] = torch.from_numpy(velodyne.load_velodyne_points(self.resolve(sample['velodyne'])))
+            ret['velodyne_P'] = torch.from_numpy(sample['velodyne_P'].copy())
+            ret['velodyne_size'] = torch.tensor(sample['velodyne_size'], dtype=torch.int32)
+        elif sample.get('groundtruth'):
             ret['groundtruth'] = self.load_img(sample['groundtruth'], gt=True)[0]
         elif self.native_gt and self.raw:
             ret['groundtruth'] = torch.zeros(1, og_h, og_w)      # no map: no valid pixel (evaluate_depth leaves the image out)
@@ -427,6 +470,10 @@ class UnSupKittiFiles(KittiDataset):
                                  'groundtruth': parts[3] if len(parts) > 3 else None})
             if self.stereo:
                 self.samples[-1].update(stereo=self.stereo_twin(parts[0]), stereo_baseline=self.baseline_of(parts[0]))
+            if self.velodyne_gt:
+                override = parts[3] if len(parts) > 3 and parts[3].endswith(".bin") else None
+                P, hw = self.velo_calib_of(parts[0])
+                self.samples[-1].update(groundtruth=None, velodyne=self.velodyne_scan(parts[0], override), velodyne_P=P, velodyne_size=hw)
 
 
 def raw_collate(samples):
@@ -441,7 +488,9 @@ class PrefetchLoader:
     and hands the trainer finished batches in the reference's collated layout (tgt [B,3,h,w], ref_imgs 2 x [B,3,h,w], intrinsics [B,3,3] fp64,
     groundtruth [B,1,h,w]) together with the event the consumer's stream has to wait on.  SURVEY.md 8f row 1, second half.
     native_groundtruth (datasets.groundtruth: native): the maps differ in size, so groundtruth is [B,1,Hmax,Wmax], each map zero-padded at
-    its bottom and right, and 'groundtruth_size' [B,2] int32 (host) holds every map's true (H, W).
+    its bottom and right, and 'groundtruth_size' [B,2] int32 (host) holds every map's true (H, W).  Samples that carry raw Velodyne scans
+    (datasets.groundtruth: velodyne) give the same layout: the scans are copied in one pinned buffer and projected on the loader's stream
+    (geometry.velodyne.depth_maps), mirrored within the true width for flipped samples.
     augment (an Augmentation): each batch also carries 'tgt_aug', 'ref_imgs_aug' (what the networks see) and 'augment_records' (host, one
     AUGMENT_RECORD per sample); a flipped sample's frames, ground truth (within its true size) and principal point (cx' = w - 1 - cx: the
     warp samples pixel centres 0..w-1) are mirrored.  Call set_epoch(epoch) before each pass: the records are drawn for (seed, rank, epoch).
@@ -508,7 +557,17 @@ class PrefetchLoader:
             K = K.to(self.device, non_blocking=True)
             if rng is not None:
                 extra['tgt_aug'], extra['ref_imgs_aug'] = out_aug[:B], [out_aug[B:2 * B], out_aug[2 * B:]]
-            if self.native_groundtruth:
+            if 'velodyne' in samples[0]:
+                # datasets.groundtruth: velodyne -- the batch's scans in one pinned buffer, one copy, the maps projected on this stream
+                scans = [s['velodyne'] for s in samples]
+                offsets = np.concatenate([[0], np.cumsum([len(p) for p in scans])]).astype(np.int64)
+                host = torch.empty((int(offsets[-1]), 4), dtype=torch.float32, pin_memory=True)
+                torch.cat(scans, out=host)
+                sizes = torch.stack([s['velodyne_size'] for s in samples]).to(torch.int32)
+                gt = velodyne.depth_maps(host.to(self.device, non_blocking=True), offsets, torch.stack([s['velodyne_P'] for s in samples]),
+                                         sizes.numpy(), flip=flip if flip.any() else None, device=self.device)
+                extra['groundtruth_size'] = sizes
+            elif self.native_groundtruth:
                 maps = [s['groundtruth'].flip(-1) if flip[i] else s['groundtruth'] for i, s in enumerate(samples)]
                 sizes = torch.tensor([tuple(m.shape[-2:]) for m in maps], dtype=torch.int32)
                 host = torch.zeros((B, 1, int(sizes[:, 0].max()), int(sizes[:, 1].max())), dtype=torch.float32).pin_memory()

@@ -146,7 +146,7 @@ class Trainer:
         if getattr(self.dataset, "raw", False):
             # file-backed samples decoded to uint8 on the host (worker processes); resize + normalise on the GPU, one batch ahead
             from dataloaders import PrefetchLoader, raw_collate
-            native = bool(getattr(self.dataset, "native_gt", False))
+            native = bool(getattr(self.dataset, "native_gt", False))      # (datasets.groundtruth: native or velodyne)
             mk = lambda idx, drop, aug=None: PrefetchLoader(torch.utils.data.DataLoader(self.dataset, batch_size=self.batch_size,
                                                                                       sampler=SequentialIndicesSampler(idx),
                                                                                       num_workers=self.num_workers, drop_last=drop,
@@ -315,8 +315,8 @@ class Trainer:
         try:
             for samples in self.validation_loader:
                 if 'groundtruth_size' not in samples:
-                    raise ValueError("validation: the KITTI protocol needs the native ground truth (datasets.groundtruth: native with a KITTI "
-                                     "split); this loader gives ground truth resized to the network's input")
+                    raise ValueError("validation: the KITTI protocol needs the native ground truth (datasets.groundtruth: native or velodyne with "
+                                     "a KITTI split); this loader gives ground truth resized to the network's input")
                 tgt = samples['tgt'].to(self.device, non_blocking=True)
                 gt = samples['groundtruth'].to(self.device, non_blocking=True)
                 rows.append(eval_depth_rows(gt, self.depth_model(tgt), samples['groundtruth_size'], v['crop'], v['min_depth'], v['max_depth'],
