@@ -63,10 +63,10 @@ typedef struct mcav_igemm_desc {
     const float* addend;    /* same layout as y */
     int pool;               /* 1: destination pixels are visited in 2x2 blocks and summed: y is [B, Hd/2, Wd/2, Cd] */
     float* stats;           /* NULL or [mtiles][2][n_count]: per-tile column sums of y and y^2 (BatchNorm batch statistics) */
-    int tile;               /* 0 = choose automatically; else a tile-config id in the low byte; bits 8-15 = test / tuning switches that force or forbid one
+    int tile;               /* 0 = choose automatically; else a tile-config id in the low byte; bits 8-16 = test / tuning switches that force or forbid one
                              * of the kernel forms (bit 13: the fp32 patch-in-LDS kernel for 3x3 stride-1 zero-padded launches; bit 14: the second
                              * patch kernel of the split form -- 128- / 256-row tiles, LDS-DMA filter ring, one workgroup per CU --, bit 15: its
-                             * 128 x 32 configuration at two workgroups per CU) */
+                             * 128 x 32 configuration at two workgroups per CU; bit 16: the depth stem with the shared 4-byte-store epilogue) */
     int groups;             /* 0/1 = one group.  G > 1: the batch is G equal groups (e.g. the tgt and ref0 passes of the depth net run as
                              * one launch); output tiles never straddle a group, so `stats` rows [g * mtiles/G, (g+1) * mtiles/G) belong to
                              * group g (per-pass BatchNorm statistics).  Only with the DIRECT / SMALLC gathers and pool == 0. */
@@ -276,6 +276,24 @@ int mcav_bn_bwd_apply(const float* dy, const float* y_act, const float* x, const
 int mcav_maxpool3s2_fwd(const float* x, int B, int H, int W, int C, float* y, uint8_t* idx, void* stream);
 /* dx (+)= scatter of dy through idx, gathered per input pixel; then multiplied by (xact > 0) when relu_mask != NULL... */
 int mcav_maxpool3s2_bwd(const float* dy, const uint8_t* idx, int B, int H, int W, int C, float* dx, int accumulate, void* stream);
+
+/* The ResNet stem around conv1 (C = 64 only; anything else is MCAV_E_INVALID): the passes above fused so that the largest activation of
+ * the network is moved as rarely as the results allow.  Element for element the arithmetic and its order are those of the calls they stand
+ * for, so every output is bit-identical to theirs.  groups: passes stacked along the batch (scale / shift / save_* are [groups][C]).
+ * forward = mcav_bn_apply(x, RELU) -> y, then mcav_maxpool3s2_fwd(y) -> pooled, idx, reading x once. */
+int mcav_stem_bn_relu_pool_fwd(const float* x, const float* scale, const float* shift, int B, int H, int W, int C, int groups, float* y,
+                               float* pooled, uint8_t* idx, void* stream);
+/* backward, pass A = mcav_maxpool3s2_bwd(dpooled, idx, dx = dy, accumulate) then mcav_bn_bwd_reduce(relu) without the gradient map in
+ * between: dz = (dy + gathered dpooled) * (x * scale + shift > 0) stays in registers; sums / dgamma / dbeta as mcav_bn_bwd_reduce
+ * (workspace: mcav_bn_bwd_workspace_bytes).  store_dz: dz is also written over dy, for mcav_bn_bwd_apply(dy, relu = 0) to read. */
+int mcav_stem_pool_bn_bwd_reduce(float* dy, const float* dpooled, const uint8_t* idx, const float* x, const float* scale, const float* shift,
+                                 const float* save_mean, const float* save_invstd, int B, int H, int W, int C, int groups, int store_dz,
+                                 float* dgamma, float* dbeta, int accumulate, float* sums /* [groups][2][C] out */, void* workspace,
+                                 size_t workspace_bytes, void* stream);
+/* backward, pass B = the same gather and mask from the untouched dy, then mcav_bn_bwd_apply's formula -> dx */
+int mcav_stem_pool_bn_bwd_apply(const float* dy, const float* dpooled, const uint8_t* idx, const float* x, const float* scale,
+                                const float* shift, const float* gamma, const float* save_mean, const float* save_invstd, const float* sums,
+                                int B, int H, int W, int C, int groups, float* dx, void* stream);
 
 /* elementwise helpers on flat buffers */
 int mcav_act_bwd(const float* dy, const float* y, int act, size_t n, float* dx, int accumulate, void* stream);

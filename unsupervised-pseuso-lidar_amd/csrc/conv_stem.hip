@@ -33,7 +33,99 @@ struct StemCfg {
 using StemDepth = StemCfg<3, 4, 64, 8>;           // torchvision conv1 on the NHWC4 image
 using StemPose = StemCfg<9, 16, 16, 4>;           // PoseNet conv1 on the 16-channel (9 real) input pack
 
-template <class S>
+// The depth stem's epilogue with 16-byte stores.  The accumulator layout makes lanes output channels and registers pixels, so the shared
+// lean epilogue stores 4 bytes per lane: 16 store instructions per 32 x 32 block.  Here the four values a lane holds for one register quad
+// (pixels r .. r + 3 of its channel) are transposed across the four lanes of a DPP quad (channels 4 m .. 4 m + 3): lane 4 m + e then holds
+// pixel r + e for those four channels, one 16-byte store, and a store instruction covers 8 pixels x 128 contiguous bytes.  The values, the
+// statistics and the order they are summed in are the lean epilogue's (the column sums are taken before the transpose), so the output
+// and the statistics slab are bit-identical to it.  Only what stem_kind() admits: no pool / aux / addend, y_choff = 0, all 64 columns.
+template <int CTRL>
+__device__ __forceinline__ float quad_perm(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+
+__device__ __forceinline__ void quad_transpose4(float (&v)[4], int lane) {
+    const bool odd = lane & 1, hi = lane & 2;
+#pragma unroll
+    for (int a = 0; a < 4; a += 2) {              // 2 x 2 blocks: registers (a, a + 1) against lane ^ 1
+        const float got = quad_perm<0xB1>(odd ? v[a] : v[a + 1]);
+        v[a] = odd ? got : v[a];
+        v[a + 1] = odd ? v[a + 1] : got;
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {                 // the 2 x 2 blocks themselves: registers (a, a + 2) against lane ^ 2
+        const float got = quad_perm<0x4E>(hi ? v[a] : v[a + 2]);
+        v[a] = hi ? got : v[a];
+        v[a + 2] = hi ? v[a + 2] : got;
+    }
+}
+
+template <class T>
+__device__ __forceinline__ void stem_epilogue_wide(const IgemmParams& p, typename T::AccT (&acc)[T::TM][T::TN], const unsigned* s_outb,
+                                                   float (*s_stat)[2][T::BN], int tid, int wm0, int mt) {
+    static_assert(T::MF == 32 && T::WAVES_N == 1, "the depth stem's tile");
+    constexpr int BN = T::BN, NQ = T::ACC / 4;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int ccol = lane & 31, l4 = lane & 3;
+    const __amdgpu_buffer_rsrc_t ry = make_rsrc(p.y, (unsigned)((size_t)p.g.B * p.Hd * p.Wd * p.Cd * 4));
+    float ssum[T::TN], ssq[T::TN];
+#pragma unroll
+    for (int j = 0; j < T::TN; ++j) { ssum[j] = 0.f; ssq[j] = 0.f; }
+#pragma unroll
+    for (int i = 0; i < T::TM; ++i)
+#pragma unroll
+        for (int j = 0; j < T::TN; ++j) {
+            __builtin_amdgcn_sched_barrier(0);
+            const int nl = j * 32 + ccol;
+            const float bv = p.bias ? p.bias[nl] : 0.f;
+            const unsigned colb = (unsigned)(nl - l4) * 4u;
+#pragma unroll
+            for (int q = 0; q < NQ; ++q) {
+                const u32x4 ro = *reinterpret_cast<const u32x4*>(&s_outb[wm0 + i * 32 + 8 * q + 4 * (lane >> 5)]);
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float s = acc[i][j][4 * q + e] + bv;
+                    if (p.act == MCAV_ACT_RELU) s = fmaxf(s, 0.f);
+                    else if (p.act != MCAV_ACT_NONE) s = act_fwd(s, p.act);
+                    v[e] = s;
+                    if (p.stats) {
+#pragma clang fp contract(off)      // the lean epilogue's square is a product of its own (it selects between two products before the add): same rounding here
+                        const float sv = ro[e] != OOB ? s : 0.f;
+                        ssum[j] += sv;
+                        ssq[j] += sv * sv;
+                    }
+                }
+                quad_transpose4(v, lane);
+                const unsigned row = l4 == 0 ? ro.x : l4 == 1 ? ro.y : l4 == 2 ? ro.z : ro.w;
+                f32x4 o;
+                o.x = v[0]; o.y = v[1]; o.z = v[2]; o.w = v[3];
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), ry, (int)(row + colb), 0, 0);      // (OOB rows: dropped in hardware)
+            }
+        }
+    if (p.stats) {
+#pragma unroll
+        for (int j = 0; j < T::TN; ++j) {
+            ssum[j] += __shfl_xor(ssum[j], 32, 64);
+            ssq[j] += __shfl_xor(ssq[j], 32, 64);
+            if (lane < 32) {
+                s_stat[wave][0][j * 32 + lane] = ssum[j];
+                s_stat[wave][1][j * 32 + lane] = ssq[j];
+            }
+        }
+        __syncthreads();
+        for (int e = tid; e < 2 * BN; e += 256) {
+            const int which = e / BN, col = e - which * BN;
+            float s = 0.f;
+#pragma unroll
+            for (int wmi = 0; wmi < T::WAVES_M; ++wmi) s += s_stat[wmi][which][col];
+            p.stats[((size_t)mt * 2 + which) * p.n_count + col] = s;
+        }
+    }
+}
+
+// kWide: stem_epilogue_wide instead of the shared lean epilogue (the 64-channel depth stem; desc.tile bit 16 keeps the lean one)
+template <class S, bool kWide = false>
 __global__ __launch_bounds__(256, 2) void stem7x7s2_fwd_kernel(IgemmParams p, const float* __restrict__ wk, int tiles_x, int tiles_y) {
     constexpr int C = S::C, PR = S::PR, KS = S::KS, TM = S::TM, TN = S::TN, NW = S::NW, TH = S::TH;
     __shared__ __attribute__((aligned(16))) float sP[C][PR][2][ST_PC];
@@ -137,7 +229,8 @@ __global__ __launch_bounds__(256, 2) void stem7x7s2_fwd_kernel(IgemmParams p, co
         __syncthreads();                                  // every wavefront is done with the patch: its memory becomes the statistics scratch
         // (the lean epilogue since round 4: raw buffer stores, no per-element branch or 64-bit address arithmetic -- the stem kernels were bound by
         // their epilogue, not by the MFMAs: 0.18 of the depth stem's 0.23 ms remained with the K loop removed)
-        igemm_epilogue_lean<E>(p, acc, s_out, s_stat, tid, wave * TM * 32, 0, 0, mt);
+        if constexpr (kWide) stem_epilogue_wide<E>(p, acc, s_out, s_stat, tid, wave * TM * 32, mt);
+        else igemm_epilogue_lean<E>(p, acc, s_out, s_stat, tid, wave * TM * 32, 0, 0, mt);
     }
 }
 
@@ -498,7 +591,8 @@ bool mcav_try_stem(const mcav_igemm_desc* d, const IgemmParams& p, hipStream_t s
         }
     }
     const dim3 grid(ntiles < 512 ? ntiles : 512);         // persistent: 2 per CU
-    if (kind == 1) timed_launch(stem7x7s2_fwd_kernel<StemDepth>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y);
+    if (kind == 1 && !((d->tile >> 16) & 1)) timed_launch(stem7x7s2_fwd_kernel<StemDepth, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y);
+    else if (kind == 1) timed_launch(stem7x7s2_fwd_kernel<StemDepth>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y);
     else timed_launch(stem7x7s2_fwd_kernel<StemPose>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y);
     return true;
 }

@@ -27,8 +27,9 @@ def hw(t):
 
 
 # ------------------------------------------------------------------------------------------------ BatchNorm'd conv
-def conv_bn(conv, bn, x, stride, pad, train, relu, residual=None, smallc=False, groups=1):
-    """-> (raw conv output, BN state, activated output).  groups: independent passes stacked along the batch (per-pass statistics)."""
+def conv_bn(conv, bn, x, stride, pad, train, relu, residual=None, smallc=False, groups=1, apply=True):
+    """-> (raw conv output, BN state, activated output).  groups: independent passes stacked along the batch (per-pass statistics).
+    apply=False: the caller applies the BatchNorm itself (the stem, fused with its max-pool) -> activated output None."""
     spec = spec_of(conv, stride, pad, N.PAD_ZERO, smallc)
     if train:
         raw, slab = N.conv_fwd(spec, x, stats=True, groups=groups)
@@ -36,7 +37,7 @@ def conv_bn(conv, bn, x, stride, pad, train, relu, residual=None, smallc=False, 
     else:
         raw = N.conv_fwd(spec, x)
         st = N.bn_eval_coeffs(bn)
-    return raw, st, N.bn_apply(raw, st, relu, residual)
+    return raw, st, N.bn_apply(raw, st, relu, residual) if apply else None
 
 
 # ------------------------------------------------------------------------------------------------ BasicBlock
@@ -150,8 +151,12 @@ STAGES = ("layer1", "layer2", "layer3", "layer4")
 def encoder_forward(net, x4, train, groups=1):
     """net: ResNetParams holder; x4: NHWC4 image (groups passes stacked along the batch).  -> ([f0..f4], saved)"""
     sv = {"x4": x4}
-    sv["c1"], sv["st"], f0 = conv_bn(net.conv1, net.bn1, x4, 2, 3, train, True, smallc=True, groups=groups)
-    p0, sv["idx"] = N.maxpool_fwd(f0)
+    fuse = N.stem_fusable(net.conv1.weight.shape[0])
+    sv["c1"], sv["st"], f0 = conv_bn(net.conv1, net.bn1, x4, 2, 3, train, True, smallc=True, groups=groups, apply=not fuse)
+    if fuse:
+        f0, p0, sv["idx"] = N.stem_bn_relu_pool_fwd(sv["c1"], sv["st"])      # bn1 + ReLU + max-pool in one pass over c1
+    else:
+        p0, sv["idx"] = N.maxpool_fwd(f0)
     feats, blocks = [f0], []
     x = p0
     for si, name in enumerate(STAGES):
@@ -186,8 +191,11 @@ def encoder_backward(net, sv, dfeats, complete=False):
             if STAGES[si] in announced_stages():
                 N.grads_ready(getattr(net, STAGES[si]).parameters())
     # dcur = gradient w.r.t. the max-pool output; f0 also feeds the decoder
-    df0 = N.maxpool_bwd(dcur, sv["idx"], tuple(feats[0].shape), dx=dfeats[0], accumulate=True)
-    dc1 = N.bn_backward(net.bn1, sv["st"], df0, feats[0], sv["c1"], True)
+    if N.stem_fusable(feats[0].shape[3]) and dfeats[0] is not None and sv["st"].mean is not None:
+        dc1 = N.stem_pool_bn_backward(net.bn1, sv["st"], dfeats[0], dcur, sv["idx"], sv["c1"])      # no unmasked df0, no read of f0
+    else:
+        df0 = N.maxpool_bwd(dcur, sv["idx"], tuple(feats[0].shape), dx=dfeats[0], accumulate=True)
+        dc1 = N.bn_backward(net.bn1, sv["st"], df0, feats[0], sv["c1"], True)
     N.conv_wgrad(spec_of(net.conv1, 2, 3, N.PAD_ZERO, True), sv["x4"], dc1)
 
 

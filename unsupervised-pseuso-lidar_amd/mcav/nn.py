@@ -78,6 +78,9 @@ L.register({
     "mcav_bn_bwd_finalize": (c_i, [c_p, c_i, c_i, c_p, c_p, c_i, c_p, c_i, c_p]),
     "mcav_maxpool3s2_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p]),
     "mcav_maxpool3s2_bwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p]),
+    "mcav_stem_bn_relu_pool_fwd": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p]),
+    "mcav_stem_pool_bn_bwd_reduce": (c_i, [c_p] * 8 + [c_i] * 6 + [c_p, c_p, c_i, c_p, c_p, c_sz, c_p]),
+    "mcav_stem_pool_bn_bwd_apply": (c_i, [c_p] * 10 + [c_i] * 5 + [c_p, c_p]),
     "mcav_act_bwd": (c_i, [c_p, c_p, c_i, c_sz, c_p, c_i, c_p]),
     "mcav_act_bwd_strided": (c_i, [c_p, c_p, c_i, c_sz, c_p, c_i, c_p]),
     "mcav_conv3x3r_c1_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p]),
@@ -997,6 +1000,51 @@ def maxpool_bwd(dy, idx, in_shape, dx=None, accumulate=False):
         dx = empty(in_shape, dy)
         accumulate = False
     L.check(L.lib().mcav_maxpool3s2_bwd(P(dy), P(idx), B, H, W, C, P(dx), int(accumulate), L.stream()), "mcav_maxpool3s2_bwd")
+    return dx
+
+
+# ------------------------------------------------------------------------------------------------ the stem around conv1 (csrc/stem_ops.hip)
+STEM_FUSE = _os.environ.get("MCAV_STEM_FUSE", "1") != "0"          # 0: bn_apply, maxpool_fwd / maxpool_bwd, bn_backward as separate passes (A/B timing)
+# the backward's second pass: 0 = pass A leaves the masked gradient in place of dy and mcav_bn_bwd_apply reads it; 1 = pass B gathers and masks again
+STEM_BWD_REGATHER = _os.environ.get("MCAV_STEM_BWD_REGATHER", "0") != "0"
+
+
+def stem_fusable(C):
+    """BatchNorm + ReLU + MaxPool(3, 2, 1) on a 64-channel map (every torchvision ResNet's stem) takes the fused stem kernels."""
+    return STEM_FUSE and C == 64
+
+
+def stem_bn_relu_pool_fwd(x, st):
+    """-> (relu(bn(x)), its 3x3 s2 p1 max-pool, the winning taps): bn_apply(x, st, True) and maxpool_fwd of it, bit for bit, in one pass over x."""
+    B, H, W, C = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.empty_like(x)
+    pooled = empty((B, Ho, Wo, C), x)
+    idx = torch.empty((B, Ho, Wo, C), dtype=torch.uint8, device=x.device)
+    L.check(L.lib().mcav_stem_bn_relu_pool_fwd(P(x), P(st.scale), P(st.shift), B, H, W, C, st.groups, P(y), P(pooled), P(idx), L.stream()),
+            "mcav_stem_bn_relu_pool_fwd")
+    return y, pooled, idx
+
+
+def stem_pool_bn_backward(bn, st, dy, dpooled, idx, x, regather=None):
+    """Backward of stem_bn_relu_pool_fwd for a train-mode BatchNorm -> dx (gradient at the raw conv output x).  dy: the gradient reaching the
+    activated map from elsewhere (consumed: overwritten unless regather); dpooled: the gradient at the pooled map.  Accumulates dgamma / dbeta."""
+    B, H, W, C = x.shape
+    h = L.lib()
+    G = st.groups
+    regather = STEM_BWD_REGATHER if regather is None else regather
+    ws = L.workspace(h.mcav_bn_bwd_workspace_bytes(B * H * W, C, G), x.device, "bn_bwd")
+    sums = empty((G, 2, C), x)
+    gg, gb = grad_buffer(bn.weight), grad_buffer(bn.bias)
+    L.check(h.mcav_stem_pool_bn_bwd_reduce(P(dy), P(dpooled), P(idx), P(x), P(st.scale), P(st.shift), P(st.mean), P(st.invstd), B, H, W, C, G,
+                                           int(not regather), P(gg), P(gb), 1, P(sums), P(ws), ws.numel(), L.stream()), "mcav_stem_pool_bn_bwd_reduce")
+    dx = torch.empty_like(x)
+    if regather:
+        L.check(h.mcav_stem_pool_bn_bwd_apply(P(dy), P(dpooled), P(idx), P(x), P(st.scale), P(st.shift), P(bn.weight), P(st.mean), P(st.invstd),
+                                              P(sums), B, H, W, C, G, P(dx), L.stream()), "mcav_stem_pool_bn_bwd_apply")
+    else:
+        L.check(h.mcav_bn_bwd_apply(P(dy), None, P(x), P(bn.weight), P(st.mean), P(st.invstd), P(sums), 0, B * H * W, C, P(dx), None, 0, G, L.stream()),
+                "mcav_bn_bwd_apply")
     return dx
 
 
