@@ -150,6 +150,32 @@ int mcav_invert_pose(const float* T, int B, float* Tinv, void* stream);
 int mcav_disp_to_depth(const float* disp, float* depth, size_t n, void* stream);
 int mcav_disp_to_depth_bwd(const float* disp, const float* d_depth, float* d_disp, size_t n, void* stream);
 
+/* The depth pyramid of the multi-scale loss: the coarse disparity maps of up to MCAV_PYR_MAX_LEVELS decoder scales -> full-resolution
+ * depths, one launch forward and one backward, in place of one mcav_disp_to_depth + one mcav_resize_bilinear_fwd (and their backwards)
+ * per scale and per depth pass.
+ * levels: HOST array of nlevels records, copied into the kernel arguments (no device table, no copy: the call can be captured).
+ *   disp:   device [B,h,w] sigmoid disparities, 1 <= h <= H, 1 <= w <= W (upsampling only, as mcav_resize_bilinear_bwd);
+ *   d_disp: device [B,h,w], written by the backward (the forward ignores it).
+ * B is the stacked batch: the maps of the target and the reference pass of one scale are one [2B,h,w] buffer.
+ * out, d_out: device [nlevels][B][H][W].  With R = bilinear resize to H x W (F.interpolate, align_corners=False: the taps of
+ * mcav_resize_bilinear_fwd with scale = h / H in float32) and D(d) = 1 / (10 d + 0.01) (mcav_disp_to_depth):
+ *   default (the reference's order, losses.py:212-216):  out_l = R(D(disp_l)),  d_disp_l = D'(disp_l) * R^T(d_out_l)
+ *   MCAV_PYR_RESIZE_THEN_DEPTH (monodepth2's order):     out_l = D(R(disp_l)),  d_disp_l = R^T(-10 out_l^2 * d_out_l)
+ * The backward reads `out` only under MCAV_PYR_RESIZE_THEN_DEPTH (it may be NULL otherwise) and `disp` only in the default order.
+ * No workspace, no host synchronisation, no atomics: every sum runs in a fixed order (along x, then along y), results are bit-identical
+ * from run to run.  Returns MCAV_E_INVALID for a null pointer, nlevels outside [1, MCAV_PYR_MAX_LEVELS], a non-positive size, h > H or
+ * w > W, unknown flag bits or B * H * W >= 2^31; nothing is launched then. */
+#define MCAV_PYR_MAX_LEVELS 3
+#define MCAV_PYR_RESIZE_THEN_DEPTH 1
+typedef struct mcav_pyr_level {
+    const float* disp;
+    float* d_disp;
+    int h, w;
+} mcav_pyr_level;
+int mcav_depth_pyramid_fwd(const mcav_pyr_level* levels, int nlevels, int B, int H, int W, unsigned flags, float* out, void* stream);
+int mcav_depth_pyramid_bwd(const mcav_pyr_level* levels, int nlevels, int B, int H, int W, unsigned flags, const float* out,
+                           const float* d_out, void* stream);
+
 /* SSIM.standard_loss (losses.py:12-54): x, y [N,H,W] planes (N = B*C) -> clamp((1-SSIM)/2, 0, 1). */
 int mcav_ssim_fwd(const float* x, const float* y, int N, int H, int W, float C1, float C2, float* out, void* stream);
 

@@ -2,6 +2,7 @@
 // channel copy (concat / slice), bilinear resize of 1-channel maps (align_corners = False) and its adjoint,
 // affine map, elementwise product, per-channel column sums.
 #include "conv_gather.h"
+#include "pyramid_math.h"
 
 namespace mcav {
 
@@ -22,15 +23,7 @@ __global__ void copy_channels_kernel(const float* src, size_t n_pix, int Cs, int
     }
 }
 
-// PyTorch's bilinear source index with align_corners = False: max(0, scale * (dst + 0.5) - 0.5)
-__device__ __forceinline__ void bil_src(int o, float scale, int n_in, int& i0, int& i1, float& lam) {
-    float s = scale * ((float)o + 0.5f) - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    i0 = (int)s;
-    if (i0 > n_in - 1) i0 = n_in - 1;
-    i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
-    lam = s - (float)i0;
-}
+using pyr::bil_src;      // PyTorch's bilinear source index with align_corners = False (pyramid_math.h, shared with depth_pyramid.hip)
 
 __global__ void resize_bilinear_fwd_kernel(const float* src, int B, int h, int w, float* dst, int H, int W, float sy, float sx) {
     const size_t total = (size_t)B * H * W;

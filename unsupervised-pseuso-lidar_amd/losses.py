@@ -18,7 +18,10 @@ from mcav import lib as L
 
 class _WarpLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, disp_t, disp_r, poses, tgt, ref0, ref1, K, flags, term_weights, selection=None, stereo=None, baseline=None):
+    def forward(ctx, disp_t, disp_r, poses, tgt, ref0, ref1, K, flags, term_weights, selection=None, stereo=None, baseline=None,
+                grad_out=None):
+        """grad_out: optional pair of preallocated tensors (shaped like disp_t, disp_r) that receive the gradients w.r.t. the two maps -- the
+        depth pyramid's gradient buffer (mcav/multiscale.py), whose backward then reads them where they lie."""
         B, _, H, W = tgt.shape
         for n, t in (("tgt", tgt), ("ref0", ref0), ("ref1", ref1), ("disp_t", disp_t), ("disp_r", disp_r), ("poses", poses)):
             L.dev(t, n)
@@ -33,8 +36,13 @@ class _WarpLossFn(torch.autograd.Function):
         h = L.lib()
         ws = L.workspace(h.mcav_warp_loss_workspace_bytes(B, H, W), tgt.device, "warp_loss", zero=True)
         losses = torch.empty(2, dtype=torch.float32, device=tgt.device)
-        g_dt = torch.empty_like(disp_t)
-        g_dr = torch.empty_like(disp_r)
+        if grad_out is not None:
+            g_dt, g_dr = (L.dev(g, "grad_out") for g in grad_out)
+            if g_dt.shape != disp_t.shape or g_dr.shape != disp_r.shape:
+                raise L.MCAVError("grad_out: one tensor shaped like each depth map")
+        else:
+            g_dt = torch.empty_like(disp_t)
+            g_dr = torch.empty_like(disp_r)
         g_p = torch.empty_like(poses)
         tw = (ctypes.c_float * len(term_weights))(*term_weights)
         args = [L.ptr(tgt), L.ptr(ref0), L.ptr(ref1), L.ptr(disp_t), L.ptr(disp_r), L.ptr(poses), L.ptr(K), B, H, W]
@@ -84,7 +92,7 @@ class _WarpLossFn(torch.autograd.Function):
                     "mcav_warp_loss_masked_fwd_bwd(bwd)")
         else:
             L.check(L.lib().mcav_warp_loss_fwd_bwd(*args, flags | L.WL_SKIP_IF_UNIT, L.ptr(up), *tail), "mcav_warp_loss_fwd_bwd(bwd)")
-        return g_dt, g_dr, g_p, None, None, None, None, None, None, None, None, None
+        return g_dt, g_dr, g_p, None, None, None, None, None, None, None, None, None, None
 
 
 STEREO_TERM_WEIGHTS = (1 / 6, 1 / 6, 0.5, 1 / 6)      # (tw0, tw1, tw2, tws): the target-view group is the mean of its three warps
@@ -128,10 +136,17 @@ class Losses:
     joins warps 0 and 1 -- in their per-pixel minimum under `min_reprojection`, with its own identity error under `automask` -- and its known
     metric baseline makes the learnt depth metric: what pseudo-LiDAR needs.  Term weights (1/6, 1/6, 1/6 and 1/2 for warp 2) / n_scales;
     selection code 3 = the stereo warp.  b is the x of the stereo camera's centre in the target camera's frame (KITTI left target: +0.54),
-    negated for a mirrored sample."""
+    negated for a mirrored sample.
+
+    `multiscale_upsample` / `fused_pyramid` (attributes as well; trainer config `loss: {multiscale_upsample: depth|disparity, fused_pyramid:
+    true}`) act when the depth net returns several scales (DispNetS, DispResNet(scales=n)): every coarse scale is evaluated at full
+    resolution, as D_s = resize(1 / (10 d_s + 0.01)) ("depth", the reference's order, losses.py:212-216; the default) or as
+    D_s = 1 / (10 resize(d_s) + 0.01) ("disparity", monodepth2's).  With `fused_pyramid` the coarse scales of both depth passes go through
+    one forward and one backward launch (include/mcav_depth.h: mcav_depth_pyramid_fwd / _bwd) instead of a launch per scale, pass, operation
+    and direction; the loss is the same."""
 
     def __init__(self, ssim=False, min_reprojection=False, automask=False, keep_selection=False, edge_aware_smoothness=False,
-                 edge_smoothness_weight=1e-3, stereo=False):
+                 edge_smoothness_weight=1e-3, stereo=False, multiscale_upsample="depth", fused_pyramid=False):
         self.clip_loss = 0.5
         self.stereo = bool(stereo)
         self.ssim = bool(ssim)
@@ -141,6 +156,10 @@ class Losses:
         self.selection = None
         self.edge_aware_smoothness = bool(edge_aware_smoothness)
         self.edge_smoothness_weight = float(edge_smoothness_weight)
+        if multiscale_upsample not in ("depth", "disparity"):
+            raise ValueError("multiscale_upsample must be 'depth' or 'disparity', got %r" % (multiscale_upsample,))
+        self.multiscale_upsample = multiscale_upsample
+        self.fused_pyramid = bool(fused_pyramid)
 
     def _flags(self, n_scales):
         return L.WL_SSIM if self.ssim else 0
@@ -182,7 +201,8 @@ class Losses:
             sel = [] if self.keep_selection else None
             out = multiscale_losses(tgt_img, ref_imgs, disparity, poses, intrinsics, ssim=self.ssim, min_reprojection=self.min_reprojection,
                                     automask=self.automask, selections=sel, edge_aware_smoothness=self.edge_aware_smoothness,
-                                    edge_smoothness_weight=self.edge_smoothness_weight, stereo=st, stereo_baseline=sb)
+                                    edge_smoothness_weight=self.edge_smoothness_weight, stereo=st, stereo_baseline=sb,
+                                    multiscale_upsample=self.multiscale_upsample, fused_pyramid=self.fused_pyramid)
             if sel is not None:
                 self.selection = sel
             return out

@@ -16,6 +16,12 @@ c_sz = ctypes.c_size_t
 
 WL_K_F64, WL_SKIP_IF_UNIT, WL_NO_SMOOTH, WL_INPUT_DEPTH, WL_SSIM = 1, 2, 4, 8, 16
 WL_MIN_REPROJ, WL_AUTOMASK = 32, 64      # mcav_warp_loss_masked_fwd_bwd only
+PYR_MAX_LEVELS, PYR_RESIZE_THEN_DEPTH = 3, 1
+
+
+class PyrLevel(ctypes.Structure):
+    """mcav_pyr_level (include/mcav_depth.h): one coarse scale of mcav_depth_pyramid_fwd / _bwd."""
+    _fields_ = [("disp", c_p), ("d_disp", c_p), ("h", c_i), ("w", c_i)]
 
 
 class MCAVError(RuntimeError):
@@ -37,6 +43,8 @@ _SIGNATURES = {
     "mcav_project": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_u, c_p, c_p]),
     "mcav_disp_to_depth": (c_i, [c_p, c_p, c_sz, c_p]),
     "mcav_disp_to_depth_bwd": (c_i, [c_p, c_p, c_p, c_sz, c_p]),
+    "mcav_depth_pyramid_fwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_u, c_p, c_p]),
+    "mcav_depth_pyramid_bwd": (c_i, [c_p, c_i, c_i, c_i, c_i, c_u, c_p, c_p, c_p]),
     "mcav_ssim_fwd": (c_i, [c_p, c_p, c_i, c_i, c_i, c_f, c_f, c_p, c_p]),
     "mcav_smooth_workspace_bytes": (c_sz, [c_i, c_i, c_i]),
     "mcav_smooth_loss_fwd_bwd": (c_i, [c_p, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_p, c_sz, c_p]),

@@ -178,22 +178,40 @@ class DepthDecoder(nn.Module):
         return self.outputs
 
 
+def _as_maps(disps, scales):
+    """{scale: NHWC [B,h,w,1]} -> the [B,1,h,w] maps of `scales` (NHWC with C = 1 is NCHW)."""
+    return [disps[s].view(disps[s].shape[0], 1, disps[s].shape[1], disps[s].shape[2]) for s in scales]
+
+
+def _head_grads(scales, grads):
+    """Incoming [B,1,h,w] gradients -> decoder_backward's {scale: NHWC gradient}.  A scale without a gradient is left out; scale 0, where
+    the decoder's backward chain starts, gets zeros then."""
+    dd = {}
+    for s, g in zip(scales, grads):
+        if g is not None:
+            g = L.dev(g.contiguous(), "grad")
+            dd[s] = g.view(g.shape[0], g.shape[2], g.shape[3], 1)
+    if 0 not in dd:
+        s, g = next(iter(dd.items()))
+        dd[0] = torch.zeros((g.shape[0], g.shape[1] << s, g.shape[2] << s, 1), dtype=g.dtype, device=g.device)
+    return dd
+
+
 class _DispResNetFn(torch.autograd.Function):
-    """Whole depth net as one autograd node: image -> disparity (scale 0)."""
+    """Whole depth net as one autograd node: image -> the disparities of mod.active_scales() (scale 0 first)."""
 
     @staticmethod
     def forward(ctx, x, mod, *params):
+        scales = mod.active_scales()
         feats, esv = E.encoder_forward(mod.encoder.encoder, _to_nhwc4(x), mod.training)
-        disps, dsv = E.decoder_forward(mod.decoder, feats, (0,))
-        ctx.mod, ctx.esv, ctx.dsv = mod, esv, dsv
-        d = disps[0]
-        return d.view(d.shape[0], 1, d.shape[1], d.shape[2])       # NHWC with C = 1 is NCHW
+        disps, dsv = E.decoder_forward(mod.decoder, feats, scales)
+        ctx.mod, ctx.esv, ctx.dsv, ctx.scales = mod, esv, dsv, scales
+        return tuple(_as_maps(disps, scales))
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, *gs):
         mod = ctx.mod
-        g = L.dev(g.contiguous(), "grad")
-        dfe = E.decoder_backward(mod.decoder, ctx.dsv, {0: g.view(g.shape[0], g.shape[2], g.shape[3], 1)})
+        dfe = E.decoder_backward(mod.decoder, ctx.dsv, _head_grads(ctx.scales, gs))
         E.encoder_backward(mod.encoder.encoder, ctx.esv, dfe)
         ctx.esv = ctx.dsv = None
         return (None, None) + (None,) * len(list(mod.parameters()))
@@ -203,7 +221,8 @@ class _DispResNetPairFn(torch.autograd.Function):
     """Two independent passes (e.g. tgt and ref0, trainer.py:296-299) as ONE set of launches over the stacked batch.
 
     BatchNorm statistics stay per pass (the conv epilogue's statistic tiles never straddle a pass; running statistics are
-    updated pass 0 first, then pass 1), so the result equals two separate calls, at half the launches and twice the rows per GEMM."""
+    updated pass 0 first, then pass 1), so the result equals two separate calls, at half the launches and twice the rows per GEMM.
+    Outputs: pass 0's maps of every active scale, then pass 1's; the two maps of a scale are the halves of one stacked buffer."""
 
     @staticmethod
     def forward(ctx, xa, xb, mod, *params):
@@ -211,27 +230,31 @@ class _DispResNetPairFn(torch.autograd.Function):
         if xa.shape != xb.shape or xa.shape[1] != 3:
             raise L.MCAVError("forward_pair: two [B,3,H,W] image batches of one shape")
         B = xa.shape[0]
+        scales = mod.active_scales()
         x4 = torch.zeros((2 * B, xa.shape[2], xa.shape[3], 4), dtype=torch.float32, device=xa.device)      # (the kernel keeps channel 3 as it finds it)
         N.nchw_to_nhwc(xa, 4, x4[:B])                  # both passes into ONE stacked NHWC4 buffer (no concatenation pass)
         N.nchw_to_nhwc(xb, 4, x4[B:])
         feats, esv = E.encoder_forward(mod.encoder.encoder, x4, mod.training, groups=2)
-        disps, dsv = E.decoder_forward(mod.decoder, feats, (0,))
-        ctx.mod, ctx.esv, ctx.dsv = mod, esv, dsv
-        d = disps[0]
-        d = d.view(d.shape[0], 1, d.shape[1], d.shape[2])
-        B = xa.shape[0]
-        return d[:B], d[B:]
+        disps, dsv = E.decoder_forward(mod.decoder, feats, scales)
+        ctx.mod, ctx.esv, ctx.dsv, ctx.scales = mod, esv, dsv, scales
+        maps = _as_maps(disps, scales)
+        return tuple(d[:B] for d in maps) + tuple(d[B:] for d in maps)
 
     @staticmethod
-    def backward(ctx, ga, gb):
+    def backward(ctx, *gs):
         mod = ctx.mod
-        if ga is None or gb is None:
+        n = len(ctx.scales)
+        stacked = []
+        for ga, gb in zip(gs[:n], gs[n:]):
+            if ga is None and gb is None:
+                stacked.append(None)
+                continue
             ref = ga if ga is not None else gb
             ga = torch.zeros_like(ref) if ga is None else ga
             gb = torch.zeros_like(ref) if gb is None else gb
-        g = torch.cat([L.dev(ga.contiguous(), "grad"), L.dev(gb.contiguous(), "grad")], 0)
-        dfe = E.decoder_backward(mod.decoder, ctx.dsv, {0: g.view(g.shape[0], g.shape[2], g.shape[3], 1)})
-        if N.GRADS_READY is not None:                   # both passes are in this one backward: the decoder's gradients are final
+            stacked.append(torch.cat([L.dev(ga.contiguous(), "grad"), L.dev(gb.contiguous(), "grad")], 0))
+        dfe = E.decoder_backward(mod.decoder, ctx.dsv, _head_grads(ctx.scales, stacked))
+        if N.GRADS_READY is not None:                   # both passes are in this one backward: the decoder's gradients (every head's) are final
             from mcav.dist import announced_stages
             if "decoder" in announced_stages():
                 N.grads_ready(mod.decoder.parameters())
@@ -241,22 +264,32 @@ class _DispResNetPairFn(torch.autograd.Function):
 
 
 class DispResNet(nn.Module):
-    def __init__(self, num_layers=18, dtype=None):
+    def __init__(self, num_layers=18, dtype=None, scales=1):
         """The reference hard-codes ResNet-18 (resnet_dispnet.py:101); num_layers=50 is BASELINE.json's configs[3] extension.
-        dtype=torch.bfloat16 opts into the bf16 MFMA conv tiles of configs[2] / [4] (mcav.nn.set_compute_dtype); default fp32 as the reference."""
+        dtype=torch.bfloat16 opts into the bf16 MFMA conv tiles of configs[2] / [4] (mcav.nn.set_compute_dtype); default fp32 as the reference.
+        scales: how many decoder scales (0 .. scales-1, disp_s [B,1,H>>s,W>>s]) a TRAINING forward returns -- monodepth2's multi-scale loss
+        takes 4.  The reference returns scale 0 only (resnet_dispnet.py:107): the default.  In eval mode only scale 0 is computed, whatever
+        `scales` is.  All four heads are parameters either way: state_dict keys and shapes do not depend on `scales`."""
         super().__init__()
+        if isinstance(scales, bool) or not isinstance(scales, int) or not 1 <= scales <= 4:
+            raise ValueError("DispResNet: scales must be an integer from 1 to 4, got %r" % (scales,))
+        self.scales = scales
         self.encoder = ResnetEncoder(num_layers, True)
         self.decoder = DepthDecoder(self.encoder.num_ch_enc)
         if dtype is not None:
             N.set_compute_dtype(self, dtype)
 
+    def active_scales(self):
+        return tuple(range(self.scales)) if self.training else (0,)
+
     def forward(self, x):
-        return [_DispResNetFn.apply(x, self, *self.parameters())]
+        return list(_DispResNetFn.apply(x, self, *self.parameters()))
 
     def forward_pair(self, xa, xb):
         """== (self(xa), self(xb)) evaluated in that order, as one stacked launch set (see _DispResNetPairFn)."""
-        da, db = _DispResNetPairFn.apply(xa, xb, self, *self.parameters())
-        return [da], [db]
+        out = _DispResNetPairFn.apply(xa, xb, self, *self.parameters())
+        n = len(out) // 2
+        return list(out[:n]), list(out[n:])
 
 
 class DispResNet50(DispResNet):
@@ -264,3 +297,17 @@ class DispResNet50(DispResNet):
 
     def __init__(self):
         super().__init__(50)
+
+
+class DispResNetMS(DispResNet):
+    """No-argument 4-scale ResNet-18 (monodepth2's multi-scale training) so a config file can name it (model.depth.name: DispResNetMS)."""
+
+    def __init__(self):
+        super().__init__(18, scales=4)
+
+
+class DispResNet50MS(DispResNet):
+    """No-argument 4-scale ResNet-50."""
+
+    def __init__(self):
+        super().__init__(50, scales=4)

@@ -78,6 +78,11 @@ class Trainer:
         self.criterion.automask = bool((config.get('loss') or {}).get('automask', False))                   # and identity auto-masking
         self.criterion.edge_aware_smoothness = bool((config.get('loss') or {}).get('edge_aware_smoothness', False))   # monodepth2's smoothness
         self.criterion.edge_smoothness_weight = float((config.get('loss') or {}).get('edge_smoothness_weight', 1e-3))
+        self.criterion.fused_pyramid = bool((config.get('loss') or {}).get('fused_pyramid', False))       # multi-scale nets: one launch pair
+        upsample = (config.get('loss') or {}).get('multiscale_upsample', 'depth')                           # depth (reference) | disparity (monodepth2)
+        if upsample not in ('depth', 'disparity'):
+            raise ValueError("config loss.multiscale_upsample must be depth or disparity, got %r" % (upsample,))
+        self.criterion.multiscale_upsample = upsample
         from dataloaders import stereo_from_config
         self.criterion.stereo = stereo_from_config(config)      # opt-in mono + stereo (metric depth): batches carry 'stereo' / 'stereo_baseline'
         self.validation = self.validation_config(config.get('validation'))      # opt-in KITTI protocol for validate()
@@ -130,7 +135,14 @@ class Trainer:
                 model = obj
         if model is None:
             raise ValueError("config: no class %s in models.%s.%s" % (model_name, model_type, config['model'][model_type]['file']))
-        model = model()
+        scales = config['model'][model_type].get('scales')
+        if scales is None:
+            model = model()
+        else:                  # model.depth.scales: how many decoder scales the net returns in training (DispResNet(scales=n))
+            import inspect
+            if 'scales' not in inspect.signature(model.__init__).parameters:
+                raise ValueError("config model.%s.scales: %s takes no `scales` argument" % (model_type, model_name))
+            model = model(scales=int(scales))
         if self.train_from_scratch and model_type != 'depth':
             model.init_weights()
         return model.to(self.device)
