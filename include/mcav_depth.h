@@ -209,6 +209,63 @@ int mcav_edge_smooth_fwd(const float* disp, const float* img, int B, int H, int 
 int mcav_edge_smooth_bwd(const float* disp, const float* img, int B, int H, int W, int h, int w, float weight, const double* saved,
                          const float* upstream, float* d_disp, int accumulate, void* stream);
 
+/* Depth geometry consistency (SC-SfMLearner, Bian et al., NeurIPS 2019, compute_pairwise_loss / mean_on_mask): the two depth maps of a
+ * training step must agree with each other through the pose, which keeps the scale of the prediction from drifting between frames.  The
+ * definition is tests/geom_consistency_ref.py.  Two directions d, the geometries of the fused loss kernel's warps 0 and 2:
+ *   d = 0: a = tgt, b = ref0, [R|t] = pose[:,0];      d = 1: a = ref0, b = tgt, [R|t] = the rigid inverse of pose[:,0].
+ * For every pixel p = (x, y) of a, with D = 1 / (10 disp + 0.01) (or the inputs themselves under MCAV_WL_INPUT_DEPTH):
+ *   c        = P [K^-1 [x y 1]^T D_a(p) ; 1],  P = K [R|t]
+ *   (ix, iy) = the sampling position of mcav_warp_loss_fwd_bwd for that warp: c0 / (c2 + 1e-5), c1 / (c2 + 1e-5) through the
+ *              normalise / un-normalise round trip, align_corners=True -- the same position and bilinear cell, bit for bit
+ *   D_proj   = c2,   D_samp = the bilinear sample of D_b at (ix, iy), zero outside the image
+ *   valid    = 0 <= ix <= W-1 && 0 <= iy <= H-1 && D_proj >= 1e-3   (NaN: not valid)
+ *   diff     = |D_proj - D_samp| / (D_proj + D_samp)                 (|.|' at 0 is 0)
+ *   n_d = number of valid pixels over the batch,  E_d = sum(valid * diff) / n_d if n_d > min_valid, else 0 with zero gradients
+ *   loss_gc  = 0.5 (E_0 + E_1)
+ * SC-SfMLearner clamps D_proj at 1e-3 where this drops the pixel (a clamped pixel has no gradient through D_proj either); its
+ * mean_on_mask uses min_valid = 100.  The count carries no gradient.
+ *
+ * disp_t, disp_r0: [B,1,H,W]; poses: [B,2,6] (pose[:,1] takes no part: its gradient is 0); K: [B,3,3] fp64 (MCAV_WL_K_F64) or fp32.
+ * flags: MCAV_WL_K_F64 | MCAV_WL_INPUT_DEPTH | MCAV_GC_LDS_TILE.  With MCAV_WL_INPUT_DEPTH the depths must be > 1/16 (see the scatter
+ * below); depths from disparities are >= 0.0999.  MCAV_GC_LDS_TILE selects the backward's second scatter form (the forward ignores it):
+ * the taps of a 32 x 32 tile of a are first added into an LDS copy of the same tile of b plus a halo of 8 and flushed with one global add
+ * per non-zero texel; taps beyond the halo go straight to global memory.  Integer sums: both forms give the same bits.
+ * mcav_geom_consistency_fwd: loss_accum[0] += weight * loss_gc (one float on the device, the += contract of mcav_edge_smooth_fwd).
+ *   saved: 4 + 24 B doubles on the DEVICE, read by the backward: n_0, n_1, sum(valid diff)_0, _1, then the raw (unnormalised) sums
+ *     d diff / dP [B][2][12].  Nothing comes back to the host.
+ *   diff_out: optional [B,2,H,W] float (NULL = not written): diff of direction d in plane d, -1 where the pixel is not valid.
+ *     1 - diff is SC-SfMLearner's weight mask.
+ *   One memset node (the completion tickets) and one launch.  The per-workgroup partial sums (sum of diff, the valid count as an
+ *   integer, the 12 dP sums) are added in float64 in a fixed order: every output is bit-identical from run to run.  diff_out, n_d
+ *   (integers) and with them every gradient of a sample do not depend on where the sample sits in the batch; the float64 sums of diff
+ *   over the samples are added in an order fixed by the sample INDEX, so permuting a batch of three or more samples can move saved[2..3]
+ *   and the loss in the last bit (two samples: a + b = b + a).
+ * mcav_geom_consistency_bwd: the same inputs and `saved`; upstream: one float on the DEVICE (NULL means 1).  With
+ *   k_d = upstream * weight * 0.5 / n_d (0 when n_d <= min_valid):
+ *     d_disp_t  (+)= k_0 direct_0 + k_1 scattered_1,    d_disp_r0 (+)= k_1 direct_1 + k_0 scattered_0    (times -10 D^2 for disparities)
+ *     d_poses[:,0] (+)= the pose gradient of k_0 dP_0 and, through the inverse, k_1 dP_1;  d_poses[:,1] (+)= 0
+ *   direct_d: d diff / d D_a through D_proj and through the sampling position; scattered_d: the adjoint of the bilinear gather, each
+ *   tap's w_tap * d diff / d D_samp added to its texel of D_b.  That sum is formed in 64-bit FIXED POINT: the contribution is clamped to
+ *   [-(8 - 2^-21), 8 - 2^-21], converted with llrint(g * 2^36) and added as an integer, so it does not depend on the order of arrival (no float atomics).
+ *   |d diff / d D_samp| <= 1 / (2 D_samp) <= 5.005 for depths from disparities, and < 8 for depths > 1/16: the clamp never acts there;
+ *   a texel receives at most one tap per pixel of a, so |sum| <= (8 - 2^-21) * 2^36 * H*W < 2^63 for H*W <= 2^24: no overflow.  accumulate != 0 adds into the three outputs.
+ *   One memset node (the accumulators) and two launches (scatter, combine).
+ * The workspace is scratch for the duration of one call (tickets, slab, accumulators: 24 B H W bytes and change); it needs no zero-fill
+ * and carries nothing from one call to the next: a forward never depends on what an earlier call left behind.  One call at a time per
+ * workspace.  No host synchronisation, allocation or copy: both calls can be captured in a hipGraph.
+ * Both return MCAV_E_INVALID for a null pointer (diff_out and upstream excepted), unknown flag bits, min_valid < 0, B <= 0, B > 4095,
+ * H < 2, W < 2 or H*W > 2^24, and MCAV_E_WORKSPACE for a workspace below mcav_geom_consistency_workspace_bytes(B, H, W) (which is 0 for
+ * a rejected shape).  Nothing is launched then. */
+#define MCAV_GC_LDS_TILE 256u
+size_t mcav_geom_consistency_workspace_bytes(int B, int H, int W);
+int mcav_geom_consistency_fwd(const float* disp_t, const float* disp_r0, const float* poses, const void* K, int B, int H, int W,
+                              unsigned flags, int min_valid, float weight, double* saved, float* loss_accum, float* diff_out,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int mcav_geom_consistency_bwd(const float* disp_t, const float* disp_r0, const float* poses, const void* K, int B, int H, int W,
+                              unsigned flags, int min_valid, float weight, const double* saved, const float* upstream,
+                              float* d_disp_t, float* d_disp_r0, float* d_poses, int accumulate,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- after the training step ------------------------------------------------------------------ */
 
 /* Depth metrics, reference evaluate.py:6-39 (compute_errors): one pass over the ground-truth depth and the network's sigmoid

@@ -58,6 +58,7 @@ __device__ __forceinline__ void handoff_store(double* p, double v) { __hip_atomi
 __device__ __forceinline__ void handoff_store(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float handoff_load(const float* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double handoff_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ unsigned handoff_load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void handoff_release() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // compiler ordering (and LDS) ...
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // ... and this thread's global stores have been acknowledged

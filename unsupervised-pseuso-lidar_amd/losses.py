@@ -95,6 +95,57 @@ class _WarpLossFn(torch.autograd.Function):
         return g_dt, g_dr, g_p, None, None, None, None, None, None, None, None, None, None
 
 
+L.register({
+    "mcav_geom_consistency_workspace_bytes": (L.c_sz, [L.c_i, L.c_i, L.c_i]),
+    "mcav_geom_consistency_fwd": (L.c_i, [L.c_p] * 4 + [L.c_i, L.c_i, L.c_i, L.c_u, L.c_i, L.c_f, L.c_p, L.c_p, L.c_p, L.c_p, L.c_sz, L.c_p]),
+    "mcav_geom_consistency_bwd": (L.c_i, [L.c_p] * 4 + [L.c_i, L.c_i, L.c_i, L.c_u, L.c_i, L.c_f, L.c_p, L.c_p, L.c_p, L.c_p, L.c_p, L.c_i,
+                                          L.c_p, L.c_sz, L.c_p]),
+})
+
+
+class _GeomConsistencyFn(torch.autograd.Function):
+    """SC-SfMLearner's depth geometry consistency between the two depth maps of a step (include/mcav_depth.h: mcav_geom_consistency_fwd /
+    _bwd) -> weight * loss_gc.  The forward leaves its counts and sums on the device (`saved`); the backward reads them and autograd's
+    upstream from there: no host sync, both capturable.  diff_out: optional [B,2,H,W] float tensor that receives the per-pixel diff."""
+
+    @staticmethod
+    def forward(ctx, disp_t, disp_r, poses, K, flags, min_valid, weight, diff_out=None):
+        for n, t in (("disp_t", disp_t), ("disp_r", disp_r), ("poses", poses)):
+            L.dev(t, n)
+        L.dev(K, "intrinsics", K.dtype)
+        if K.dtype == torch.float64:
+            flags |= L.WL_K_F64
+        B, C, H, W = disp_t.shape
+        if C != 1 or disp_r.shape != disp_t.shape or tuple(poses.shape) != (B, 2, 6) or tuple(K.shape) != (B, 3, 3):
+            raise L.MCAVError("geometry consistency expects two [B,1,H,W] maps, poses [B,2,6] and intrinsics [B,3,3]")
+        if diff_out is not None:
+            L.dev(diff_out, "consistency")
+            if tuple(diff_out.shape) != (B, 2, H, W):
+                raise L.MCAVError("geometry consistency: the diff planes are [B,2,H,W]")
+        h = L.lib()
+        dev = disp_t.device
+        ws = L.workspace(max(h.mcav_geom_consistency_workspace_bytes(B, H, W), 1), dev, "geom_consistency")
+        saved = torch.empty(4 + 24 * B, dtype=torch.float64, device=dev)
+        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        args = [L.ptr(disp_t), L.ptr(disp_r), L.ptr(poses), L.ptr(K), B, H, W, flags, int(min_valid), float(weight), L.ptr(saved)]
+        L.check(h.mcav_geom_consistency_fwd(*args, L.ptr(loss), L.ptr(diff_out), L.ptr(ws), ws.numel(), L.stream()),
+                "mcav_geom_consistency_fwd")
+        ctx.keep = (args, (disp_t, disp_r, poses, K, saved))
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        args, (disp_t, disp_r, poses, K, saved) = ctx.keep
+        h = L.lib()
+        B, _, H, W = disp_t.shape
+        up = g.reshape(1).to(torch.float32).contiguous()
+        ws = L.workspace(max(h.mcav_geom_consistency_workspace_bytes(B, H, W), 1), disp_t.device, "geom_consistency")
+        g_dt, g_dr, g_p = torch.empty_like(disp_t), torch.empty_like(disp_r), torch.empty_like(poses)
+        L.check(h.mcav_geom_consistency_bwd(*args, L.ptr(up), L.ptr(g_dt), L.ptr(g_dr), L.ptr(g_p), 0, L.ptr(ws), ws.numel(), L.stream()),
+                "mcav_geom_consistency_bwd")
+        return g_dt, g_dr, g_p, None, None, None, None, None
+
+
 STEREO_TERM_WEIGHTS = (1 / 6, 1 / 6, 0.5, 1 / 6)      # (tw0, tw1, tw2, tws): the target-view group is the mean of its three warps
 
 
@@ -146,8 +197,14 @@ class Losses:
     and direction; the loss is the same."""
 
     def __init__(self, ssim=False, min_reprojection=False, automask=False, keep_selection=False, edge_aware_smoothness=False,
-                 edge_smoothness_weight=1e-3, stereo=False, multiscale_upsample="depth", fused_pyramid=False):
+                 edge_smoothness_weight=1e-3, stereo=False, multiscale_upsample="depth", fused_pyramid=False,
+                 geometry_consistency=False, geometry_consistency_weight=0.5, geometry_min_valid=100, keep_consistency=False):
         self.clip_loss = 0.5
+        self.geometry_consistency = bool(geometry_consistency)
+        self.geometry_consistency_weight = float(geometry_consistency_weight)
+        self.geometry_min_valid = int(geometry_min_valid)
+        self.keep_consistency = bool(keep_consistency)
+        self.consistency = None
         self.stereo = bool(stereo)
         self.ssim = bool(ssim)
         self.min_reprojection = bool(min_reprojection)
@@ -189,8 +246,32 @@ class Losses:
         return stereo.contiguous(), b
 
     def forward(self, tgt_img, ref_imgs, disparity, poses, intrinsics, gt=None, stereo=None, stereo_baseline=None):
-        """-> [loss_mam, loss_smooth].  disparity = [disps(tgt), disps(ref0)], each a list over scales.  stereo / stereo_baseline: the
-        stereo frame [B,3,H,W] and its baseline [B] (metres), used (and required) when `.stereo` is set."""
+        """-> [loss_mam, loss_smooth] (and the weighted geometry-consistency term when `.geometry_consistency` is set).  disparity =
+        [disps(tgt), disps(ref0)], each a list over scales.  stereo / stereo_baseline: the stereo frame [B,3,H,W] and its baseline [B]
+        (metres), used (and required) when `.stereo` is set."""
+        out = self._forward(tgt_img, ref_imgs, disparity, poses, intrinsics, stereo, stereo_baseline)
+        if self.geometry_consistency:
+            if disparity[0][0].shape[-2:] != tgt_img.shape[-2:] or disparity[1][0].shape[-2:] != tgt_img.shape[-2:]:
+                raise L.MCAVError("geometry consistency acts on scale 0 of both depth passes at the image's resolution (the intrinsics' own)")
+            out = list(out) + [self.geometry_consistency_loss(disparity[0][0], disparity[1][0], poses, intrinsics)]
+        return out
+
+    def geometry_consistency_loss(self, disp_t, disp_r, poses, intrinsics, inputs_are_depth=False, lds_tile=False):
+        """geometry_consistency_weight * loss_gc of two full-resolution [B,1,H,W] maps (sigmoid disparities, or depths with
+        inputs_are_depth) under poses[:,0] and the intrinsics of that resolution.  lds_tile: the backward's scatter goes through an
+        LDS tile (MCAV_GC_LDS_TILE) instead of four global adds per pixel: the same bits, another schedule (tools/geom_bench.py)."""
+        diff = None
+        if self.keep_consistency:
+            B, _, H, W = disp_t.shape
+            diff = torch.empty((B, 2, H, W), dtype=torch.float32, device=disp_t.device)
+        loss = _GeomConsistencyFn.apply(disp_t.contiguous(), disp_r.contiguous(), poses.contiguous(), intrinsics.contiguous(),
+                                        (L.WL_INPUT_DEPTH if inputs_are_depth else 0) | (L.GC_LDS_TILE if lds_tile else 0), self.geometry_min_valid,
+                                        self.geometry_consistency_weight, diff)
+        if diff is not None:
+            self.consistency = diff
+        return loss
+
+    def _forward(self, tgt_img, ref_imgs, disparity, poses, intrinsics, stereo=None, stereo_baseline=None):
         st, sb = self._stereo_inputs(tgt_img, stereo, stereo_baseline)
         disp_t, disp_r = disparity[0], disparity[1]
         n = len(disp_t)

@@ -17,6 +17,7 @@ c_sz = ctypes.c_size_t
 WL_K_F64, WL_SKIP_IF_UNIT, WL_NO_SMOOTH, WL_INPUT_DEPTH, WL_SSIM = 1, 2, 4, 8, 16
 WL_MIN_REPROJ, WL_AUTOMASK = 32, 64      # mcav_warp_loss_masked_fwd_bwd only
 PYR_MAX_LEVELS, PYR_RESIZE_THEN_DEPTH = 3, 1
+GC_LDS_TILE = 256                      # mcav_geom_consistency_bwd: the LDS-tile form of the scatter
 
 
 class PyrLevel(ctypes.Structure):

@@ -78,6 +78,9 @@ class Trainer:
         self.criterion.automask = bool((config.get('loss') or {}).get('automask', False))                   # and identity auto-masking
         self.criterion.edge_aware_smoothness = bool((config.get('loss') or {}).get('edge_aware_smoothness', False))   # monodepth2's smoothness
         self.criterion.edge_smoothness_weight = float((config.get('loss') or {}).get('edge_smoothness_weight', 1e-3))
+        self.criterion.geometry_consistency = bool((config.get('loss') or {}).get('geometry_consistency', False))   # SC-SfMLearner's depth consistency
+        self.criterion.geometry_consistency_weight = float((config.get('loss') or {}).get('geometry_consistency_weight', 0.5))
+        self.criterion.geometry_min_valid = int((config.get('loss') or {}).get('geometry_min_valid', 100))
         self.criterion.fused_pyramid = bool((config.get('loss') or {}).get('fused_pyramid', False))       # multi-scale nets: one launch pair
         upsample = (config.get('loss') or {}).get('multiscale_upsample', 'depth')                           # depth (reference) | disparity (monodepth2)
         if upsample not in ('depth', 'disparity'):
