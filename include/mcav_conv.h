@@ -102,6 +102,14 @@ typedef struct mcav_igemm_desc {
     const float* w_stem;    /* NULL, or mcav_pack_stem_weights' copy of the filter: the 7x7 stride-2 stems (the image stem: SMALLC gather, 3 -> 64;
                              * PoseNet conv1: 9 of 16 stored channels -> 16) then run on the patch-in-LDS kernels of conv_stem.hip; ignored by
                              * every other launch */
+    /* The source as the NCHW images themselves (all zero = x1 is read).  Only the two 7x7 stride-2 stem launches (w_stem; the weight gradient's
+     * stem kernels) accept these; every other launch is MCAV_E_INVALID with any of them set.  x1 may then be NULL; C1 / Kp / mode describe the
+     * NHWC tensor that is no longer packed (4 channels SMALLC for the depth stem, 16 for PoseNet), B / Hs / Ws the logical source.  Results are
+     * bit-identical to the launch on the packed tensor (the kernels de-interleave their patch into channel planes either way). */
+    const float* x_planar[3];   /* up to three contiguous [planar_B][3][Hs][Ws] tensors */
+    int planar_B;               /* images per tensor (Bp) */
+    int planar_stack;           /* 1 = stacked along the batch: image b is image b % Bp of x_planar[b / Bp] (the depth stem's tgt | ref0; B % Bp == 0);
+                                 * 2 = stacked along the channels: channel c is channel c % 3 of x_planar[c / 3] (PoseNet's tgt, ref0, ref1; Bp == B) */
 } mcav_igemm_desc;
 
 /* number of M-tiles (rows of `stats`) the launch will use with its chosen tile config */
@@ -141,6 +149,29 @@ typedef struct mcav_wgrad_desc {
                              *    every other launch runs the fp32 MFMA kernels.  mcav_wgrad_uses_bf16() tells which.
                              * 3: the split form on every launch the bf16 kernels cover (parity tests).
                              * (1 takes the same patch kernel in its one-plane form where it applies.) */
+    /* BatchNorm BACKWARD, second pass, folded into the load of dy (all zero = dy is used as it is).  When set, dy is the MASKED gradient at the
+     * BatchNorm's output -- what mcav_stem_pool_bn_bwd_reduce(store_dz = 1) leaves in place of its dy -- and every element is replaced, on its
+     * way into the kernel's LDS tile, by mcav_bn_bwd_apply's
+     *   (gamma * invstd) * (g - s1 * inv_count - xhat * (s2 * inv_count)),   xhat = (x - mean) * invstd
+     * (the same device function, csrc/bn_bwd_formula.h: bit-identical to mcav_bn_bwd_apply(relu = 0) followed by the plain launch), so the
+     * gradient at the raw conv output is never written: the first layer of a network has no data gradient and this launch was its only reader.
+     * Implemented by the depth stem's kernel only (7x7 stride 2, SMALLC, 3 -> 64); every other launch, and dbias != NULL (conv1 has no
+     * bias), and a dy that is not exactly the 64 channels (dy_choff != 0 or Cdy != 64), is MCAV_E_INVALID with any of the fields set. */
+    const float* dy_bn_x;       /* the raw output of the convolution whose weight gradient this is (c1), same layout as dy */
+    const float* dy_bn_gamma;   /* [Cout] */
+    const float* dy_bn_mean;    /* [groups][Cout] */
+    const float* dy_bn_invstd;  /* [groups][Cout] */
+    const float* dy_bn_sums;    /* [groups][2][Cout]: what mcav_bn_bwd_finalize leaves (sum g, sum g * xhat) */
+    int dy_bn_groups;           /* passes stacked along the batch (B % groups == 0): image b belongs to group b / (B / groups) */
+    float dy_bn_inv_count;      /* 1 / (pixels per channel and group), rounded to float as mcav_bn_bwd_apply does: (float)(1.0 / (double)(n_pix / groups)) */
+    /* The source as the NCHW images themselves (all zero = x1 is read).  Only the two 7x7 stride-2 stem launches (w_stem; the weight gradient's
+     * stem kernels) accept these; every other launch is MCAV_E_INVALID with any of them set.  x1 may then be NULL; C1 / Kp / mode describe the
+     * NHWC tensor that is no longer packed (4 channels SMALLC for the depth stem, 16 for PoseNet), B / Hs / Ws the logical source.  Results are
+     * bit-identical to the launch on the packed tensor (the kernels de-interleave their patch into channel planes either way). */
+    const float* x_planar[3];   /* up to three contiguous [planar_B][3][Hs][Ws] tensors */
+    int planar_B;               /* images per tensor (Bp) */
+    int planar_stack;           /* 1 = stacked along the batch: image b is image b % Bp of x_planar[b / Bp] (the depth stem's tgt | ref0; B % Bp == 0);
+                                 * 2 = stacked along the channels: channel c is channel c % 3 of x_planar[c / 3] (PoseNet's tgt, ref0, ref1; Bp == B) */
 } mcav_wgrad_desc;
 
 size_t mcav_wgrad_workspace_bytes(const mcav_wgrad_desc* d);

@@ -1967,9 +1967,15 @@ int mcav_patch_f32_mtiles(const mcav_igemm_desc* d);              // conv_bf16.h
 bool mcav_try_patch_f32(const mcav_igemm_desc* d, hipStream_t s);
 int mcav_stem_mtiles(const mcav_igemm_desc* d);                   // conv_stem.hip: 0 = not the image stem
 
+int mcav_stem_planar_igemm(const mcav_igemm_desc* d);      // conv_stem.hip
+
 MCAV_EXPORT int mcav_igemm_mtiles(const mcav_igemm_desc* d) {
     IgemmParams p;
     int tile;
+    const int planar = mcav_stem_planar_igemm(d);
+    if (planar < 0) return MCAV_E_INVALID;
+    mcav_igemm_desc dp;
+    if (planar) { dp = *d; if (!dp.x1) dp.x1 = d->x_planar[0]; d = &dp; }
     if (!fill_params(d, p, tile)) return MCAV_E_INVALID;
     if (const int st = mcav_stem_mtiles(d)) return st;             // the stem kernel's 8 x 32 output tiles
     if (const int pt = mcav_patch_f32_mtiles(d)) return pt;         // the fp32 patch-in-LDS kernel's blocks (conv_bf16.hip)
@@ -1984,14 +1990,20 @@ bool mcav_try_halo(const mcav_igemm_desc* d, hipStream_t s);      // conv_halo.h
 int mcav_bf16_igemm(const mcav_igemm_desc* d, hipStream_t s);      // conv_bf16.hip: 1 = not eligible
 bool mcav_try_stem(const mcav_igemm_desc* d, const mcav::IgemmParams& p, hipStream_t s);      // conv_stem.hip: the 7x7 stride-2 image stem
 int mcav_stem_mtiles(const mcav_igemm_desc* d);
+int mcav_stem_planar_igemm(const mcav_igemm_desc* d);      // the x_planar fields: 0 = not set, 1 = a stem kernel reads them, -1 = refused
 bool mcav_bf16_wgrad_plan(const mcav_wgrad_desc* d, mcav::WgradPlan& pl);
 void mcav_bf16_wgrad_launch(const mcav::WgradParams& p, hipStream_t s);
 
 MCAV_EXPORT int mcav_igemm(const mcav_igemm_desc* d, void* stream) {
     IgemmParams p;
     int tile;
+    const int planar = mcav_stem_planar_igemm(d);      // NCHW image sources: only the two stem kernels read them (x1 may then be NULL)
+    if (planar < 0) return MCAV_E_INVALID;
+    mcav_igemm_desc dp;
+    if (planar) { dp = *d; if (!dp.x1) dp.x1 = d->x_planar[0]; d = &dp; }      // (a non-null stand-in for the checks below; never read)
     if (!fill_params(d, p, tile)) return MCAV_E_INVALID;
     hipStream_t s = as_stream(stream);
+    if (planar) return mcav_try_stem(d, p, s) ? launch_status() : MCAV_E_INVALID;
     if (mcav_try_halo(d, s)) return launch_status();
     if (mcav_try_stem(d, p, s)) return launch_status();
     if (mcav_try_patch_f32(d, s)) return launch_status();
@@ -2021,6 +2033,8 @@ namespace mcav {
 
 }  // namespace mcav
 int mcav_stem_wgrad_splits(const mcav_wgrad_desc* d);
+int mcav_stem_planar_wgrad(const mcav_wgrad_desc* d);      // the x_planar fields: 0 = not set, 1 = a stem kernel reads them, -1 = refused
+int mcav_stem_wgrad_bn(const mcav_wgrad_desc* d);      // the dy_bn_* fields: 0 = not set, 1 = the depth stem kernel applies them, -1 = refused
 void mcav_stem_wgrad_launch(const mcav_wgrad_desc* d, float* slab, int Ktot, int slabN, int splits, hipStream_t s);
 int mcav_halo_wgrad_splits(const mcav_wgrad_desc* d);
 void mcav_halo_wgrad_launch(const mcav_wgrad_desc* d, float* slab, int slabN, int splits, hipStream_t s);
@@ -2164,19 +2178,31 @@ inline void launch_wgrad(const WgradParams& p, bool use_tab, hipStream_t s) {
 
 MCAV_EXPORT size_t mcav_wgrad_workspace_bytes(const mcav_wgrad_desc* d) {
     WgradPlan pl;
-    if (!(d && d->mma != 0 && mcav_bf16_wgrad_plan(d, pl)) && !plan_wgrad(d, pl)) return 0;
+    const int planar = mcav_stem_planar_wgrad(d);
+    if (mcav_stem_wgrad_bn(d) < 0 || planar < 0) return 0;
+    mcav_wgrad_desc dp;
+    if (planar) { dp = *d; if (!dp.x1) dp.x1 = d->x_planar[0]; d = &dp; }      // (a non-null stand-in for the planner's checks; never read)
+    const bool special = mcav_stem_wgrad_bn(d) || planar;
+    if (!(d && d->mma != 0 && !special && mcav_bf16_wgrad_plan(d, pl)) && !plan_wgrad(d, pl)) return 0;
+    if (special && !pl.use_stem) return 0;
     return pl.slab_bytes + pl.pre_bytes;
 }
 
 MCAV_EXPORT int mcav_wgrad_uses_bf16(const mcav_wgrad_desc* d) {
     WgradPlan pl;
-    return d && d->mma != 0 && mcav_bf16_wgrad_plan(d, pl);
+    return d && d->mma != 0 && !mcav_stem_wgrad_bn(d) && !mcav_stem_planar_wgrad(d) && mcav_bf16_wgrad_plan(d, pl);
 }
 
 // the GEMM part of a weight gradient: partial tiles into the slab at `workspace`
 static int wgrad_gemm(const mcav_wgrad_desc* d, void* workspace, size_t workspace_bytes, hipStream_t s, WgradPlan& pl) {
-    const bool bf16 = d && d->mma != 0 && mcav_bf16_wgrad_plan(d, pl);      // bf16 MFMA tiles where the launch qualifies (conv_bf16.hip)
+    const int bn = mcav_stem_wgrad_bn(d);      // only the depth stem's kernel folds a BatchNorm backward into its dy tile: every other path refuses the fields
+    const int planar = mcav_stem_planar_wgrad(d);      // only the two stem kernels read NCHW image sources (x1 may then be NULL)
+    if (bn < 0 || planar < 0) return MCAV_E_INVALID;
+    mcav_wgrad_desc dp;
+    if (planar) { dp = *d; if (!dp.x1) dp.x1 = d->x_planar[0]; d = &dp; }      // (a non-null stand-in for the planner's checks; never read)
+    const bool bf16 = d && d->mma != 0 && !bn && !planar && mcav_bf16_wgrad_plan(d, pl);      // bf16 MFMA tiles where the launch qualifies (conv_bf16.hip)
     if ((!bf16 && !plan_wgrad(d, pl)) || !workspace) return MCAV_E_INVALID;
+    if ((bn || planar) && !pl.use_stem) return MCAV_E_INVALID;
     if (workspace_bytes < pl.slab_bytes + pl.pre_bytes) return MCAV_E_WORKSPACE;
     const int cin_total = d->Cin_total > 0 ? d->Cin_total : d->Cin;
     if (d->ci_offset < 0 || d->ci_offset + d->Cin > cin_total) return MCAV_E_INVALID;

@@ -11,6 +11,7 @@
 // lane-constant base plus an immediate: the loop body is ds_read_b32 + MFMA only.  The 168 x 64 filter slice sits in LDS too
 // (mcav_pack_stem_weights: [k][64], zero rows for the padding column).  Epilogue: the shared one (BatchNorm statistics per stacked pass).
 #include "conv_shared.h"
+#include "bn_bwd_formula.h"
 #include "kernel_timer.h"
 
 namespace mcav {
@@ -32,6 +33,41 @@ struct StemCfg {
 };
 using StemDepth = StemCfg<3, 4, 64, 8>;           // torchvision conv1 on the NHWC4 image
 using StemPose = StemCfg<9, 16, 16, 4>;           // PoseNet conv1 on the 16-channel (9 real) input pack
+
+// mcav_igemm_desc / mcav_wgrad_desc .x_planar: the stem reads the NCHW images themselves -- up to three contiguous [Bp][3][Hs][Ws] tensors --
+// instead of an NHWC copy packed for it.  The patch is split into per-channel LDS planes anyway, so a channel plane of the image is the layout
+// the staging wants: one dword load per (patch element, channel), consecutive lanes on consecutive columns.  C = 3 (the depth stem): the
+// sources are stacked along the batch, image b is image b % Bp of src[b / Bp] (tgt | ref0).  C = 9 (PoseNet): stacked along the channels,
+// channel c is channel c % 3 of src[c / 3] (tgt, ref0, ref1), Bp = B.
+struct StemPlanar {
+    const float* src[3];
+    int Bp;
+};
+
+// the C channel values of source pixel (sy, sx) of image b; ok = false (outside the image, or past the last tile): zeros, no memory traffic
+template <int C>
+__device__ __forceinline__ void stem_planar_load(const StemPlanar& pl, int b, int Hs, int Ws, int sy, int sx, bool ok, float (&out)[C]) {
+    static_assert(C == 3 || C == 9, "batch-stacked RGB sources or three channel-stacked ones");
+    const unsigned bytes = (unsigned)((size_t)pl.Bp * 3 * Hs * Ws * 4), plane = (unsigned)(Hs * Ws * 4);
+    if constexpr (C == 3) {
+        int bs = b / pl.Bp;
+        const int bl = b - bs * pl.Bp;
+        bs = ok ? bs : 0;
+        const float* const sp = bs == 0 ? pl.src[0] : bs == 1 ? pl.src[1] : pl.src[2];
+        const __amdgpu_buffer_rsrc_t r = make_rsrc(sp, bytes);
+        const unsigned off = ok ? (unsigned)(((bl * 3 * Hs + sy) * Ws + sx) * 4) : OOB;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[c] = buf_load1(r, off == OOB ? OOB : off + c * plane);
+    } else {
+        const unsigned off = ok ? (unsigned)(((b * 3 * Hs + sy) * Ws + sx) * 4) : OOB;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const __amdgpu_buffer_rsrc_t r = make_rsrc(pl.src[q], bytes);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) out[3 * q + c] = buf_load1(r, off == OOB ? OOB : off + c * plane);
+        }
+    }
+}
 
 // The depth stem's epilogue with 16-byte stores.  The accumulator layout makes lanes output channels and registers pixels, so the shared
 // lean epilogue stores 4 bytes per lane: 16 store instructions per 32 x 32 block.  Here the four values a lane holds for one register quad
@@ -125,8 +161,9 @@ __device__ __forceinline__ void stem_epilogue_wide(const IgemmParams& p, typenam
 }
 
 // kWide: stem_epilogue_wide instead of the shared lean epilogue (the 64-channel depth stem; desc.tile bit 16 keeps the lean one)
-template <class S, bool kWide = false>
-__global__ __launch_bounds__(256, 2) void stem7x7s2_fwd_kernel(IgemmParams p, const float* __restrict__ wk, int tiles_x, int tiles_y) {
+// kPlanar: the patch comes from the NCHW images (StemPlanar) instead of the NHWC tensor p.g.x1
+template <class S, bool kWide = false, bool kPlanar = false>
+__global__ __launch_bounds__(256, 2) void stem7x7s2_fwd_kernel(IgemmParams p, const float* __restrict__ wk, int tiles_x, int tiles_y, StemPlanar pl) {
     constexpr int C = S::C, PR = S::PR, KS = S::KS, TM = S::TM, TN = S::TN, NW = S::NW, TH = S::TH;
     __shared__ __attribute__((aligned(16))) float sP[C][PR][2][ST_PC];
     __shared__ __attribute__((aligned(16))) float sW[2 * KS][NW];
@@ -154,7 +191,8 @@ __global__ __launch_bounds__(256, 2) void stem7x7s2_fwd_kernel(IgemmParams p, co
     // ---- a tile's input patch: source rows 2 oy0 - 3 .., columns 2 ox0 - 3 ..; out-of-image pixels read as zero (zero padding).  The loads
     // of tile t + 1 are issued before the MFMA loop of tile t and stored when its readers are done.
     constexpr int PN = (PR * 2 * ST_PC + 255) / 256;
-    f32x4 pv[PN][S::LD4];
+    f32x4 pv[kPlanar ? 1 : PN][S::LD4];
+    float pq[kPlanar ? PN : 1][C];
     auto issue = [&](int t) {
         const int b = t / per_img, tr = t - b * per_img;
         const int ty = tr / tiles_x, tx = tr - ty * tiles_x;
@@ -165,9 +203,13 @@ __global__ __launch_bounds__(256, 2) void stem7x7s2_fwd_kernel(IgemmParams p, co
             const int row = i / (2 * ST_PC), col = i - row * (2 * ST_PC);          // col = 2 * index + parity
             const int sy = sy0 + row, sx = sx0 + col;
             const bool ok = t < ntiles && i < PR * 2 * ST_PC && (unsigned)sy < (unsigned)g.Hs && (unsigned)sx < (unsigned)g.Ws;
-            const unsigned off = ok ? (unsigned)(((b * g.Hs + sy) * g.Ws + sx) * S::CP * 4) : OOB;
+            if constexpr (kPlanar) {
+                stem_planar_load<C>(pl, b, g.Hs, g.Ws, sy, sx, ok, pq[j]);
+            } else {
+                const unsigned off = ok ? (unsigned)(((b * g.Hs + sy) * g.Ws + sx) * S::CP * 4) : OOB;
 #pragma unroll
-            for (int q = 0; q < S::LD4; ++q) pv[j][q] = buf_load4(rsx, off == OOB ? OOB : off + 16u * q);
+                for (int q = 0; q < S::LD4; ++q) pv[j][q] = buf_load4(rsx, off == OOB ? OOB : off + 16u * q);
+            }
         }
     };
     const int px = lane & 31, h = lane >> 5;
@@ -191,7 +233,10 @@ __global__ __launch_bounds__(256, 2) void stem7x7s2_fwd_kernel(IgemmParams p, co
             const int row = i / (2 * ST_PC), col = i - row * (2 * ST_PC);
             if (i < PR * 2 * ST_PC) {
 #pragma unroll
-                for (int c = 0; c < C; ++c) sP[c][row][col & 1][col >> 1] = pv[j][c >> 2][c & 3];
+                for (int c = 0; c < C; ++c) {
+                    if constexpr (kPlanar) sP[c][row][col & 1][col >> 1] = pq[j][c];
+                    else sP[c][row][col & 1][col >> 1] = pv[j][c >> 2][c & 3];
+                }
             }
         }
         __syncthreads();
@@ -264,7 +309,8 @@ __device__ __forceinline__ void st_split3(f32x4 v, st_u32x2& h, st_u32x2& m, st_
     h = __builtin_bit_cast(st_u32x2, hb); m = __builtin_bit_cast(st_u32x2, mb); l = __builtin_bit_cast(st_u32x2, lb);
 }
 
-__global__ __launch_bounds__(256, 1) void stem7x7s2_split_fwd_kernel(IgemmParams p, const float* __restrict__ wk, int tiles_x, int tiles_y) {
+template <bool kPlanar = false>
+__global__ __launch_bounds__(256, 1) void stem7x7s2_split_fwd_kernel(IgemmParams p, const float* __restrict__ wk, int tiles_x, int tiles_y, StemPlanar pl) {
     using S = StemDepth;
     using E = typename S::Epi;
     constexpr int TM = S::TM, TN = S::TN, TH = S::TH;
@@ -313,7 +359,13 @@ __global__ __launch_bounds__(256, 1) void stem7x7s2_split_fwd_kernel(IgemmParams
             const int row = i / SS_PCOL, col = i - row * SS_PCOL;
             const int sy = sy0 + row, sx = sx0 + col;
             const bool ok = t < ntiles && i < SS_PR * SS_PCOL && (unsigned)sy < (unsigned)g.Hs && (unsigned)sx < (unsigned)g.Ws;
-            pv[j] = buf_load4(rsx, ok ? (unsigned)(((b * g.Hs + sy) * g.Ws + sx) * S::CP * 4) : OOB);
+            if constexpr (kPlanar) {
+                float q3[3];
+                stem_planar_load<3>(pl, b, g.Hs, g.Ws, sy, sx, ok, q3);
+                pv[j] = f32x4{q3[0], q3[1], q3[2], 0.f};         // (the NHWC4 image's fourth channel is zero)
+            } else {
+                pv[j] = buf_load4(rsx, ok ? (unsigned)(((b * g.Hs + sy) * g.Ws + sx) * S::CP * 4) : OOB);
+            }
         }
     };
     const int px = lane & 31, h = lane >> 5;
@@ -419,10 +471,25 @@ constexpr int SW_PR = 2 * SW_TH + 5;              // 13 source rows
 // C / CP / N as in the forward kernel; KP = the filter's K padding in the slab layout (row = tap * KP + channel).  The 2 KS k rows are
 // split over the wavefronts as MT tiles of 32 each; N = 64: wavefront w takes output channels 32 (w & 1) .. and half of the k tiles;
 // N = 16: every wavefront takes all 16 (lanes 16-31 duplicate and are dropped) and a quarter of the k tiles.
-template <int C, int CP, int N, int KP>
+//
+// kBN (mcav_wgrad_desc.dy_bn_*; the depth stem): dy is the MASKED gradient at bn1's output and the tile is turned into the gradient at the raw
+// conv output on its way into LDS -- mcav_bn_bwd_apply's formula (bn_bwd_formula.h) on the c1 tile loaded next to it -- so that dc1 never goes
+// through HBM (conv1 has no data gradient: this kernel was its only reader).  A thread's four channels are fixed, its five coefficient
+// vectors depend on the image group of the tile only and are reloaded when the persistent walk enters another group.
+struct StemWgradBn {
+    const float* x;                               // raw conv output c1, same layout as dy
+    const float* gamma;
+    const float* mean;                            // [groups][N]
+    const float* invstd;                          // [groups][N]
+    const float* sums;                            // [groups][2][N]
+    int groups;
+    float inv_count;
+};
+
+template <int C, int CP, int N, int KP, bool kBN = false, bool kPlanar = false>
 __global__ __launch_bounds__(256) void stem7x7s2_wgrad_kernel(const float* __restrict__ x4, const float* __restrict__ dy, int B, int Hs, int Ws,
                                                               int Hd, int Wd, int Cdy, int dy_choff, float* __restrict__ slab, int Ktot, int slabN,
-                                                              int want_bias) {
+                                                              int want_bias, StemWgradBn bn, StemPlanar pl) {
     constexpr int KS = C * 7 * 4, KT = (2 * KS + 31) / 32;                      // k rows, 32-row k tiles
     constexpr int NSPLIT = N >= 64 ? 2 : 1, WPN = 4 / NSPLIT, MT = (KT + WPN - 1) / WPN;      // wavefronts per column group, k tiles per wavefront
     constexpr int LD4 = (C + 3) / 4, N4 = N / 4;
@@ -454,9 +521,15 @@ __global__ __launch_bounds__(256) void stem7x7s2_wgrad_kernel(const float* __res
     // every load of a tile is issued before the first LDS store (one memory round trip per tile), and the loads of tile t + 1 are issued
     // BEFORE the MFMA loop of tile t: they fly while the matrix pipe works and are stored once the tile's readers are done
     constexpr int PN = (SW_PR * 2 * ST_PC + 255) / 256, DN = (SW_TH * ST_TW * N4 + 255) / 256;
-    f32x4 pv[PN][LD4], dv[DN];
+    f32x4 pv[kPlanar ? 1 : PN][LD4], dv[DN];
+    float pq[kPlanar ? PN : 1][C];                       // kPlanar: the patch from the NCHW images (StemPlanar), as in the forward kernel
     f32x4 bsum = {0.f, 0.f, 0.f, 0.f};                   // bias gradient: this thread's 4 channels (tid % N4 is the same in every pass: 256 % N4 == 0)
     const int per_img = tiles_x * tiles_y;
+    static_assert(256 % N4 == 0, "a thread keeps its four channels from pass to pass");
+    f32x4 cv[kBN ? DN : 1];                              // kBN: the c1 tile, element for element next to dv
+    f32x4 bn_mu, bn_is, bn_gi, bn_s1, bn_t2;             // kBN: this thread's coefficients in the current image group
+    int bn_grp = -1;
+    const __amdgpu_buffer_rsrc_t rsc = make_rsrc(kBN ? bn.x : dy, (unsigned)((size_t)B * Hd * Wd * Cdy * 4));
     auto issue = [&](int t) {
         const int b = t / per_img, tr = t - b * per_img;
         const int ty = tr / tiles_x, tx = tr - ty * tiles_x;
@@ -469,9 +542,13 @@ __global__ __launch_bounds__(256) void stem7x7s2_wgrad_kernel(const float* __res
             const int row = e / (2 * ST_PC), col = e - row * (2 * ST_PC);
             const int sy = sy0 + row, sx = sx0 + col;
             const bool ok = live && e < SW_PR * 2 * ST_PC && (unsigned)sy < (unsigned)Hs && (unsigned)sx < (unsigned)Ws;
-            const unsigned off = ok ? (unsigned)(((b * Hs + sy) * Ws + sx) * CP * 4) : OOB;
+            if constexpr (kPlanar) {
+                stem_planar_load<C>(pl, b, Hs, Ws, sy, sx, ok, pq[j]);
+            } else {
+                const unsigned off = ok ? (unsigned)(((b * Hs + sy) * Ws + sx) * CP * 4) : OOB;
 #pragma unroll
-            for (int q = 0; q < LD4; ++q) pv[j][q] = buf_load4(rsx, off == OOB ? OOB : off + 16u * q);
+                for (int q = 0; q < LD4; ++q) pv[j][q] = buf_load4(rsx, off == OOB ? OOB : off + 16u * q);
+            }
         }
 #pragma unroll
         for (int j = 0; j < DN; ++j) {                                          // dy tile: pixels outside the image contribute zero
@@ -479,7 +556,9 @@ __global__ __launch_bounds__(256) void stem7x7s2_wgrad_kernel(const float* __res
             const int pix = e / N4, c4 = e - pix * N4;
             const int oy = oy0 + (pix >> 5), ox = ox0 + (pix & 31);
             const bool ok = live && e < SW_TH * ST_TW * N4 && oy < Hd && ox < Wd;
-            dv[j] = buf_load4(rsy, ok ? (unsigned)((((b * Hd + oy) * Wd + ox) * Cdy + dy_choff + c4 * 4) * 4) : OOB);
+            const unsigned off = ok ? (unsigned)((((b * Hd + oy) * Wd + ox) * Cdy + dy_choff + c4 * 4) * 4) : OOB;
+            dv[j] = buf_load4(rsy, off);
+            if constexpr (kBN) cv[j] = buf_load4(rsc, off);
         }
     };
     issue(blockIdx.x);
@@ -491,7 +570,32 @@ __global__ __launch_bounds__(256) void stem7x7s2_wgrad_kernel(const float* __res
             const int row = e / (2 * ST_PC), col = e - row * (2 * ST_PC);
             if (e < SW_PR * 2 * ST_PC) {
 #pragma unroll
-                for (int c = 0; c < C; ++c) sP[c][row][col & 1][col >> 1] = pv[j][c >> 2][c & 3];
+                for (int c = 0; c < C; ++c) {
+                    if constexpr (kPlanar) sP[c][row][col & 1][col >> 1] = pq[j][c];
+                    else sP[c][row][col & 1][col >> 1] = pv[j][c >> 2][c & 3];
+                }
+            }
+        }
+        if constexpr (kBN) {
+            const int b = t / per_img, tr = t - b * per_img;
+            const int ty = tr / tiles_x, tx = tr - ty * tiles_x;
+            const int oy0 = ty * SW_TH, ox0 = tx * ST_TW;
+            const int grp = b / (B / bn.groups);
+            if (grp != bn_grp) {                          // (uniform over the workgroup)
+                bn_grp = grp;
+                const int c4 = tid % N4;
+                const f32x4* const sg = reinterpret_cast<const f32x4*>(bn.sums) + (size_t)grp * 2 * N4;
+                bn_mu = reinterpret_cast<const f32x4*>(bn.mean)[grp * N4 + c4];
+                bn_is = reinterpret_cast<const f32x4*>(bn.invstd)[grp * N4 + c4];
+                bn_s1 = sg[c4];
+                bn_bwd_dx_coeffs(reinterpret_cast<const f32x4*>(bn.gamma)[c4], bn_is, sg[N4 + c4], bn.inv_count, bn_gi, bn_t2);
+            }
+#pragma unroll
+            for (int j = 0; j < DN; ++j) {                // pixels outside the image keep contributing zero (the formula maps 0 to a constant)
+                const int pix = (tid + 256 * j) / N4;
+                const bool in = oy0 + (pix >> 5) < Hd && ox0 + (pix & 31) < Wd;
+                const f32x4 dxv = bn_bwd_dx(dv[j], cv[j], bn_mu, bn_is, bn_gi, bn_s1, bn.inv_count, bn_t2);
+                dv[j] = in ? dxv : f32x4{0.f, 0.f, 0.f, 0.f};
             }
         }
 #pragma unroll
@@ -499,7 +603,7 @@ __global__ __launch_bounds__(256) void stem7x7s2_wgrad_kernel(const float* __res
             const int e = tid + 256 * j;
             if (e < SW_TH * ST_TW * N4) {
                 *reinterpret_cast<f32x4*>(&sDY[e / N4][(e % N4) * 4]) = dv[j];
-                bsum += dv[j];
+                if constexpr (!kBN) bsum += dv[j];
             }
         }
         __syncthreads();
@@ -559,9 +663,35 @@ static int stem_kind(const mcav_igemm_desc* d) {
     return 0;
 }
 
+// the x_planar fields of either descriptor for a launch of stem kind `kind`: 0 = not set, 1 = set and launchable, -1 = refused
+template <class D>
+static int stem_planar_state(const D* d, int kind) {
+    if (!d->x_planar[0] && !d->x_planar[1] && !d->x_planar[2] && !d->planar_B && !d->planar_stack) return 0;
+    if (d->planar_B <= 0 || !d->x_planar[0]) return -1;
+    if (kind == 1) {                                      // batch-stacked RGB images
+        const int ns = d->B / d->planar_B;
+        if (d->planar_stack != 1 || d->B % d->planar_B || ns > 3) return -1;
+        for (int i = 0; i < ns; ++i)
+            if (!d->x_planar[i]) return -1;
+        return 1;
+    }
+    if (kind == 2) return d->planar_stack == 2 && d->planar_B == d->B && d->x_planar[1] && d->x_planar[2] ? 1 : -1;
+    return -1;
+}
+
+template <class D>
+static StemPlanar stem_planar_args(const D* d) {
+    StemPlanar pl = {};
+    pl.src[0] = d->x_planar[0]; pl.src[1] = d->x_planar[1]; pl.src[2] = d->x_planar[2];
+    pl.Bp = d->planar_B > 0 ? d->planar_B : 1;
+    return pl;
+}
+
 }  // namespace mcav
 
 using namespace mcav;
+
+int mcav_stem_planar_igemm(const mcav_igemm_desc* d) { return d ? stem_planar_state(d, stem_kind(d)) : 0; }
 
 int mcav_stem_mtiles(const mcav_igemm_desc* d) {      // 0 = not this kernel's launch
     const int kind = stem_kind(d);
@@ -578,22 +708,32 @@ bool mcav_try_stem(const mcav_igemm_desc* d, const IgemmParams& p, hipStream_t s
     IgemmParams q = p;
     q.groups = 1;                                         // (the statistics rows of a tile are image-major: groups need nothing else)
     const int ntiles = d->B * tiles_x * tiles_y;
+    const bool planar = stem_planar_state(d, kind) == 1;      // (refused descriptors never get here: mcav_igemm checks first)
+    const StemPlanar pl = stem_planar_args(d);
     // The split form of the depth stem: measured 0.189 ms against the fp32 kernel's 0.179 (both with the lean epilogue; 24 x 192 x 640): the stem is
     // bound by its patch staging and its 189 MB of output stores, which the split kernel's ONE workgroup per CU (125 KB of LDS) has nothing to
     // overlap with, while its MFMAs take 0.06 instead of 0.10 ms.  OFF under the default mode (mma = 2); mma = 3 (the parity tests) runs it.
     static const int split_on = MCAV_KNOB_INT("MCAV_STEM_SPLIT", 0);
     if (kind == 1 && (d->mma == 3 || (d->mma == 2 && split_on))) {
-        static const bool allowed = hipFuncSetAttribute(reinterpret_cast<const void*>(stem7x7s2_split_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+        static const bool allowed = hipFuncSetAttribute(reinterpret_cast<const void*>(stem7x7s2_split_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                        (int)stem_split_lds_bytes()) == hipSuccess &&
+                                    hipFuncSetAttribute(reinterpret_cast<const void*>(stem7x7s2_split_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                         (int)stem_split_lds_bytes()) == hipSuccess;
         if (allowed) {
-            timed_launch(stem7x7s2_split_fwd_kernel, dim3(ntiles < 256 ? ntiles : 256), dim3(256), stem_split_lds_bytes(), s, q, d->w_stem, tiles_x, tiles_y);
+            const dim3 sgrid(ntiles < 256 ? ntiles : 256);
+            if (planar) timed_launch(stem7x7s2_split_fwd_kernel<true>, sgrid, dim3(256), stem_split_lds_bytes(), s, q, d->w_stem, tiles_x, tiles_y, pl);
+            else timed_launch(stem7x7s2_split_fwd_kernel<false>, sgrid, dim3(256), stem_split_lds_bytes(), s, q, d->w_stem, tiles_x, tiles_y, pl);
             return true;
         }
     }
     const dim3 grid(ntiles < 512 ? ntiles : 512);         // persistent: 2 per CU
-    if (kind == 1 && !((d->tile >> 16) & 1)) timed_launch(stem7x7s2_fwd_kernel<StemDepth, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y);
-    else if (kind == 1) timed_launch(stem7x7s2_fwd_kernel<StemDepth>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y);
-    else timed_launch(stem7x7s2_fwd_kernel<StemPose>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y);
+    const bool lean = (d->tile >> 16) & 1;
+    if (kind == 1 && !lean && planar) timed_launch(stem7x7s2_fwd_kernel<StemDepth, true, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
+    else if (kind == 1 && !lean) timed_launch(stem7x7s2_fwd_kernel<StemDepth, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
+    else if (kind == 1 && planar) timed_launch(stem7x7s2_fwd_kernel<StemDepth, false, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
+    else if (kind == 1) timed_launch(stem7x7s2_fwd_kernel<StemDepth>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
+    else if (planar) timed_launch(stem7x7s2_fwd_kernel<StemPose, false, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
+    else timed_launch(stem7x7s2_fwd_kernel<StemPose>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
     return true;
 }
 
@@ -614,6 +754,19 @@ static int stem_wgrad_kind(const mcav_wgrad_desc* d) {
     return 0;
 }
 
+// mcav_wgrad_desc.dy_bn_*: 0 = not set (all zero), 1 = set and launchable (the depth stem, no bias gradient), -1 = set and refused
+int mcav_stem_wgrad_bn(const mcav_wgrad_desc* d) {
+    if (!d) return 0;
+    if (!d->dy_bn_x && !d->dy_bn_gamma && !d->dy_bn_mean && !d->dy_bn_invstd && !d->dy_bn_sums && !d->dy_bn_groups && d->dy_bn_inv_count == 0.f) return 0;
+    if (stem_wgrad_kind(d) != 1 || d->dbias) return -1;      // (conv1 has no bias)
+    if (d->dy_choff != 0 || d->Cdy != 64) return -1;         // the coefficients are indexed by dy's own channel: dy and c1 are exactly the 64 channels
+    if (!d->dy_bn_x || !d->dy_bn_gamma || !d->dy_bn_mean || !d->dy_bn_invstd || !d->dy_bn_sums) return -1;
+    if (d->dy_bn_groups < 1 || d->B % d->dy_bn_groups || !(d->dy_bn_inv_count > 0.f)) return -1;
+    return 1;
+}
+
+int mcav_stem_planar_wgrad(const mcav_wgrad_desc* d) { return d ? stem_planar_state(d, stem_wgrad_kind(d)) : 0; }
+
 int mcav_stem_wgrad_splits(const mcav_wgrad_desc* d) {      // 0 = not applicable, else the number of slab partials (= persistent workgroups)
     if (!stem_wgrad_kind(d)) return 0;
     const long tiles = (long)d->B * ((d->Hd + SW_TH - 1) / SW_TH) * ((d->Wd + ST_TW - 1) / ST_TW);
@@ -622,10 +775,25 @@ int mcav_stem_wgrad_splits(const mcav_wgrad_desc* d) {      // 0 = not applicabl
 
 void mcav_stem_wgrad_launch(const mcav_wgrad_desc* d, float* slab, int Ktot, int slabN, int splits, hipStream_t s) {
     const int wb = d->dbias != nullptr;
-    if (stem_wgrad_kind(d) == 1)
-        timed_launch(stem7x7s2_wgrad_kernel<3, 4, 64, 4>, dim3(splits), dim3(256), 0, s, d->x1, d->dy, d->B, d->Hs, d->Ws, d->Hd, d->Wd, d->Cdy, d->dy_choff,
-                     slab, Ktot, slabN, wb);
-    else
-        timed_launch(stem7x7s2_wgrad_kernel<9, 16, 16, 16>, dim3(splits), dim3(256), 0, s, d->x1, d->dy, d->B, d->Hs, d->Ws, d->Hd, d->Wd, d->Cdy, d->dy_choff,
-                     slab, Ktot, slabN, wb);
+    const bool planar = mcav_stem_planar_wgrad(d) == 1;
+    const StemPlanar pl = stem_planar_args(d);
+    StemWgradBn bn = {};
+    const bool fold = mcav_stem_wgrad_bn(d) == 1;
+    if (fold) {
+        bn.x = d->dy_bn_x; bn.gamma = d->dy_bn_gamma; bn.mean = d->dy_bn_mean; bn.invstd = d->dy_bn_invstd; bn.sums = d->dy_bn_sums;
+        bn.groups = d->dy_bn_groups; bn.inv_count = d->dy_bn_inv_count;
+    }
+#define MCAV_STEM_WGRAD_LAUNCH(...)                                                                                                                    \
+    timed_launch(stem7x7s2_wgrad_kernel<__VA_ARGS__>, dim3(splits), dim3(256), 0, s, d->x1, d->dy, d->B, d->Hs, d->Ws, d->Hd, d->Wd, d->Cdy, d->dy_choff, \
+                 slab, Ktot, slabN, fold ? 0 : wb, bn, pl)
+    if (stem_wgrad_kind(d) == 1) {
+        if (fold && planar) MCAV_STEM_WGRAD_LAUNCH(3, 4, 64, 4, true, true);
+        else if (fold) MCAV_STEM_WGRAD_LAUNCH(3, 4, 64, 4, true, false);
+        else if (planar) MCAV_STEM_WGRAD_LAUNCH(3, 4, 64, 4, false, true);
+        else MCAV_STEM_WGRAD_LAUNCH(3, 4, 64, 4);
+    } else {
+        if (planar) MCAV_STEM_WGRAD_LAUNCH(9, 16, 16, 16, false, true);
+        else MCAV_STEM_WGRAD_LAUNCH(9, 16, 16, 16);
+    }
+#undef MCAV_STEM_WGRAD_LAUNCH
 }

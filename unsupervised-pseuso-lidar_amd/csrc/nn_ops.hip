@@ -2,6 +2,7 @@
 // MaxPool 3x3 s2, activation backward, spatial mean, fused Adam.  All NHWC, 16-byte accesses, grid-stride loops;
 // reductions are two-stage (per-block partials, fixed-order finalize in fp64) so results are run-to-run identical.
 #include "conv_gather.h"
+#include "bn_bwd_formula.h"
 
 namespace mcav {
 
@@ -351,9 +352,10 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const f32x4* dy, cons
         if (relu) g = relu_mask(g, yact[i]);
         if (dres) dres[i] = dres_acc ? dres[i] + g : g;
         const f32x4 is = invstd[grp * C4 + c];
-        const f32x4 xh = (x[i] - mean[grp * C4 + c]) * is;
         const f32x4* sg = sums + (size_t)grp * 2 * C4;
-        dx[i] = (gamma[c] * is) * (g - sg[c] * inv_count - xh * (sg[C4 + c] * inv_count));
+        f32x4 gi, t2;
+        bn_bwd_dx_coeffs(gamma[c], is, sg[C4 + c], inv_count, gi, t2);
+        dx[i] = bn_bwd_dx(g, x[i], mean[grp * C4 + c], is, gi, sg[c], inv_count, t2);      // (bn_bwd_formula.h: shared with the depth stem's weight gradient)
     }
 }
 

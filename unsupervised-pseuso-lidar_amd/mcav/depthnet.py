@@ -192,11 +192,13 @@ def encoder_backward(net, sv, dfeats, complete=False):
                 N.grads_ready(getattr(net, STAGES[si]).parameters())
     # dcur = gradient w.r.t. the max-pool output; f0 also feeds the decoder
     if N.stem_fusable(feats[0].shape[3]) and dfeats[0] is not None and sv["st"].mean is not None:
-        dc1 = N.stem_pool_bn_backward(net.bn1, sv["st"], dfeats[0], dcur, sv["idx"], sv["c1"])      # no unmasked df0, no read of f0
+        # no unmasked df0, no read of f0; conv1 is the first layer (no data gradient), so its weight gradient is dc1's only reader and applies
+        # bn1's backward formula itself (dy_bn): dc1 is then the masked gradient and the gradient at c1 is never stored
+        dc1, dy_bn = N.stem_pool_bn_backward_for_wgrad(net.bn1, sv["st"], dfeats[0], dcur, sv["idx"], sv["c1"])
     else:
         df0 = N.maxpool_bwd(dcur, sv["idx"], tuple(feats[0].shape), dx=dfeats[0], accumulate=True)
-        dc1 = N.bn_backward(net.bn1, sv["st"], df0, feats[0], sv["c1"], True)
-    N.conv_wgrad(spec_of(net.conv1, 2, 3, N.PAD_ZERO, True), sv["x4"], dc1)
+        dc1, dy_bn = N.bn_backward(net.bn1, sv["st"], df0, feats[0], sv["c1"], True), None
+    N.conv_wgrad(spec_of(net.conv1, 2, 3, N.PAD_ZERO, True), sv["x4"], dc1, dy_bn=dy_bn)
 
 
 # ------------------------------------------------------------------------------------------------ decoder

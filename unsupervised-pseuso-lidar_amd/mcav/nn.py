@@ -27,7 +27,8 @@ class IgemmDesc(ctypes.Structure):
                 ("y", c_p), ("Hd", c_i), ("Wd", c_i), ("Cd", c_i), ("n_begin", c_i), ("n_count", c_i), ("y_choff", c_i),
                 ("bias", c_p), ("act", c_i), ("dact_aux", c_p), ("dact", c_i), ("addend", c_p), ("pool", c_i), ("stats", c_p),
                 ("tile", c_i), ("groups", c_i), ("w_upmerge", c_p), ("mma", c_i), ("w16", c_p),
-                ("stats_x", c_p), ("stats_mean", c_p), ("stats_invstd", c_p), ("w_stem", c_p)]
+                ("stats_x", c_p), ("stats_mean", c_p), ("stats_invstd", c_p), ("w_stem", c_p),
+                ("x_planar", c_p * 3), ("planar_B", c_i), ("planar_stack", c_i)]
 
 
 class WgradDesc(ctypes.Structure):
@@ -36,7 +37,10 @@ class WgradDesc(ctypes.Structure):
                 ("mode", c_i), ("stride", c_i), ("sign", c_i), ("offset", c_i), ("pad_mode", c_i),
                 ("dy", c_p), ("Hd", c_i), ("Wd", c_i), ("Cdy", c_i), ("dy_choff", c_i), ("Cout", c_i), ("Cin", c_i),
                 ("dw_oihw", c_p), ("accumulate", c_i), ("dbias", c_p), ("tile", c_i), ("upm", c_i), ("Cin_total", c_i), ("ci_offset", c_i),
-                ("mma", c_i)]
+                ("mma", c_i),
+                ("dy_bn_x", c_p), ("dy_bn_gamma", c_p), ("dy_bn_mean", c_p), ("dy_bn_invstd", c_p), ("dy_bn_sums", c_p),
+                ("dy_bn_groups", c_i), ("dy_bn_inv_count", c_f),
+                ("x_planar", c_p * 3), ("planar_B", c_i), ("planar_stack", c_i)]
 
 
 class WgradReduceItem(ctypes.Structure):
@@ -412,6 +416,46 @@ def set_compute_dtype(module, dtype):
     return module
 
 
+# 1: the two 7x7 stride-2 stems read the NCHW images themselves (mcav_*_desc.x_planar) instead of an NHWC copy packed for them.  0: nchw_to_nhwc / nchw3_to_nhwc
+STEM_PLANAR = _os.environ.get("MCAV_STEM_PLANAR", "1") != "0"
+PLANAR_BATCH, PLANAR_CHANNELS = 1, 2
+
+
+class PlanarImages:
+    """NCHW image batches [Bp,3,H,W] standing in for the NHWC tensor a stem launch reads (conv_fwd / conv_wgrad take one as x1): stacked along
+    the batch (PLANAR_BATCH: the depth net's tgt | ref0 -> [n Bp, H, W, cp]) or along the channels (PLANAR_CHANNELS: PoseNet's tgt, ref0, ref1 ->
+    [Bp, H, W, cp], 9 real channels).  .shape is that of the tensor it replaces; packed() builds it for a launch that does not take the stem kernel."""
+
+    def __init__(self, images, stack, cp):
+        images = [L.dev(t.contiguous(), "image") for t in images]
+        if not 1 <= len(images) <= 3 or any(t.shape != images[0].shape or t.dtype != torch.float32 for t in images) or images[0].shape[1] != 3:
+            raise L.MCAVError("PlanarImages: one to three float32 [B,3,H,W] image batches of one shape")
+        if stack == PLANAR_CHANNELS and len(images) != 3:
+            raise L.MCAVError("PlanarImages: the channel-stacked form takes three images")
+        self.images, self.stack, self.cp = images, stack, cp
+        Bp, _, H, W = images[0].shape
+        self.shape = (Bp * (len(images) if stack == PLANAR_BATCH else 1), H, W, cp)
+        self.device, self.is_cuda = images[0].device, images[0].is_cuda
+
+    def numel(self):
+        return sum(t.numel() for t in self.images)
+
+    def fill(self, d):
+        d.x1 = None
+        for i, t in enumerate(self.images):
+            d.x_planar[i] = P(t)
+        d.planar_B, d.planar_stack = self.images[0].shape[0], self.stack
+
+    def packed(self):
+        if self.stack == PLANAR_CHANNELS:
+            return nchw3_to_nhwc(self.images[0], self.images[1], self.images[2], self.cp)
+        Bp = self.images[0].shape[0]
+        x = torch.zeros(self.shape, dtype=torch.float32, device=self.device)
+        for i, t in enumerate(self.images):
+            nchw_to_nhwc(t, self.cp, x[i * Bp:(i + 1) * Bp])
+        return x
+
+
 def stats_blocks_stem(spec, stats):
     return stats and not spec.smallc           # (only the image stem's kernel carries the BatchNorm statistics epilogue)
 
@@ -419,7 +463,8 @@ def stats_blocks_stem(spec, stats):
 def _weights_for(spec, d, transposed):
     """Fills d.w / d.w16 / d.mma of an IgemmDesc whose geometry is already set: the bf16 copy where the launch runs on the bf16 kernels."""
     if spec.mma in (MMA_BF16, MMA_SPLIT, MMA_SPLIT_ALL):
-        d.mma, d.w16, d.w = spec.mma, d.x1, d.x1          # placeholders: the eligibility test looks at the geometry only
+        ph = d.x1 or d.x_planar[0]
+        d.mma, d.w16, d.w = spec.mma, ph, ph              # placeholders: the eligibility test looks at the geometry only
         if L.lib().mcav_igemm_uses_bf16(ctypes.byref(d)):
             if spec.mma >= MMA_SPLIT:
                 w16 = spec.packed_bwd16s() if transposed else spec.packed_fwd16s()
@@ -446,6 +491,10 @@ def out_size(n, k, s, p):
 
 def conv_fwd(spec, x1, x2=None, up1=False, act=ACT_NONE, stats=False, tile=0, groups=1):
     """y = act(conv(cat(up2?(x1), x2)) + bias).  x1/x2 NHWC.  Returns y, or (y, stats_slab, mtiles) when stats."""
+    takes_stem = spec.is_stem() and not stats_blocks_stem(spec, stats) and x2 is None and not up1 and not (tile >> 9) & 1
+    planar = x1 if isinstance(x1, PlanarImages) else None
+    if planar is not None and not takes_stem:
+        x1, planar = planar.packed(), None
     B = x1.shape[0]
     Hs, Ws = (x1.shape[1] * 2, x1.shape[2] * 2) if up1 else (x1.shape[1], x1.shape[2])
     C1 = x1.shape[3]
@@ -453,7 +502,12 @@ def conv_fwd(spec, x1, x2=None, up1=False, act=ACT_NONE, stats=False, tile=0, gr
     Hd, Wd = out_size(Hs, spec.kh, spec.stride, spec.pad), out_size(Ws, spec.kw, spec.stride, spec.pad)
     y = empty((B, Hd, Wd, spec.cout), x1)
     d = IgemmDesc()
-    d.x1, d.x2 = P(x1), P(x2)
+    if planar is not None:
+        planar.fill(d)
+        LAUNCHES["fwd_planar"] += 1
+    else:
+        d.x1 = P(x1)
+    d.x2 = P(x2)
     d.B, d.Hs, d.Ws, d.C1, d.C2, d.up1 = B, Hs, Ws, C1, C2, int(up1)
     d.kh, d.kw, d.Np, d.Kp = spec.kh, spec.kw, spec.np, spec.kp
     d.mode = G_SMALLC if spec.smallc else G_DIRECT
@@ -463,7 +517,7 @@ def conv_fwd(spec, x1, x2=None, up1=False, act=ACT_NONE, stats=False, tile=0, gr
     d.tile = tile
     d.groups = groups if stats else 1
     _weights_for(spec, d, False)
-    if spec.is_stem() and not stats_blocks_stem(spec, stats) and x2 is None and not up1 and not (tile >> 9) & 1:
+    if takes_stem:
         d.w_stem = P(spec.packed_stem())               # a 7x7 stride-2 stem: patch-in-LDS kernel (tile bit 9 keeps the general one)
         if spec.mma == MMA_SPLIT_ALL and spec.smallc and spec.cout == 64:
             d.mma = spec.mma                           # the depth stem in the split form (stem7x7s2_split_fwd_kernel splits the packed fp32 slice itself): level with
@@ -593,14 +647,30 @@ def _dgrad_upsample_merged(spec, dy, in_shape, c1, dact_aux, dact, addend, tile)
     return y
 
 
-def conv_wgrad(spec, x1, dy, x2=None, up1=False, tile=0):
+LAUNCHES = _collections.Counter()      # tests: how often a launch took one of the image-boundary forms (wgrad_dy_bn, fwd_planar, wgrad_planar)
+
+
+class DyBn(_collections.namedtuple("DyBn", "x gamma mean invstd sums groups")):
+    """conv_wgrad(dy_bn=...): dy is the masked gradient at a train-mode BatchNorm's output and the launch applies the BatchNorm's backward formula
+    to it as it loads it (mcav_wgrad_desc.dy_bn_*).  x: the raw conv output; sums: [groups][2][C] of mcav_bn_bwd_finalize."""
+
+
+def conv_wgrad(spec, x1, dy, x2=None, up1=False, tile=0, dy_bn=None):
     """Accumulates d loss / d weight (OIHW) and d loss / d bias into the parameters' .grad buffers."""
+    planar = x1 if isinstance(x1, PlanarImages) else None
+    if planar is not None and not (spec.is_stem() and x2 is None and not up1 and not (tile >> 9) & 1):
+        x1, planar = planar.packed(), None
     B = x1.shape[0]
     Hs, Ws = (x1.shape[1] * 2, x1.shape[2] * 2) if up1 else (x1.shape[1], x1.shape[2])
     gw = grad_buffer(spec.weight)
     gb = grad_buffer(spec.bias) if spec.bias is not None else None
     d = WgradDesc()
-    d.x1, d.x2 = P(x1), P(x2)
+    if planar is not None:
+        planar.fill(d)
+        LAUNCHES["wgrad_planar"] += 1
+    else:
+        d.x1 = P(x1)
+    d.x2 = P(x2)
     d.B, d.Hs, d.Ws, d.C1, d.C2, d.up1 = B, Hs, Ws, x1.shape[3], (x2.shape[3] if x2 is not None else 0), int(up1)
     d.kh, d.kw, d.Kp = spec.kh, spec.kw, spec.kp
     d.mode = G_SMALLC if spec.smallc else G_DIRECT
@@ -612,6 +682,15 @@ def conv_wgrad(spec, x1, dy, x2=None, up1=False, tile=0):
     # MMA_SPLIT: the library takes the split form where it is ahead (wgrad3x3_patch_kernel: single-source 3x3 stride-1 layers of 64-channel
     # multiples) and the fp32 MFMA kernels elsewhere; MCAV_SPLIT_WGRAD=1 = the split form on every launch the bf16 kernels cover
     d.mma = MMA_SPLIT_ALL if (spec.mma == MMA_SPLIT and SPLIT_WGRAD) else (spec.mma if spec.mma in (MMA_BF16, MMA_SPLIT, MMA_SPLIT_ALL) else 0)
+    keep = ()
+    if dy_bn is not None:
+        if dy_bn.x.shape != dy.shape or x2 is not None or up1:
+            raise L.MCAVError("conv_wgrad: dy_bn needs the raw conv output in dy's layout and a single source")
+        d.dy_bn_x, d.dy_bn_gamma, d.dy_bn_mean, d.dy_bn_invstd, d.dy_bn_sums = P(dy_bn.x), P(dy_bn.gamma), P(dy_bn.mean), P(dy_bn.invstd), P(dy_bn.sums)
+        d.dy_bn_groups = dy_bn.groups
+        d.dy_bn_inv_count = 1.0 / (B * dy.shape[1] * dy.shape[2] // dy_bn.groups)      # (rounded to float by ctypes, as mcav_bn_bwd_apply's cast does)
+        keep = (dy_bn.x, dy_bn.gamma, dy_bn.mean, dy_bn.invstd, dy_bn.sums)
+        LAUNCHES["wgrad_dy_bn"] += 1
     bf16 = bool(d.mma and L.lib().mcav_wgrad_uses_bf16(ctypes.byref(d)))
     flops = 2.0 * B * dy.shape[1] * dy.shape[2] * spec.cout * spec.cin * spec.kh * spec.kw
     tag = "pix=%d Cout=%d Ktot=%dx%d s%d" % (B * dy.shape[1] * dy.shape[2], spec.cout, spec.cin, spec.kh * spec.kw, spec.stride)
@@ -645,7 +724,7 @@ def conv_wgrad(spec, x1, dy, x2=None, up1=False, tile=0):
         executed = flops * (8.0 / 7.0) * (1.0 if spec.cout >= 32 else 2.0)
     elif up1 and x2 is None and spec.kh == 3 and spec.pad_mode == PAD_REFLECT and c1 == 16 and spec.cout <= 16 and not (tile >> 9) & 1:
         executed = flops * 4.0 / 9.0                                      # level 0: conv3x3_halo_wgrad_up_kernel (merged taps)
-    launch_wgrad(d, (x1, x2, dy), flops, tag, executed)
+    launch_wgrad(d, (x1, x2, dy) + keep, flops, tag + (" [bn backward folded into dy]" if dy_bn is not None else ""), executed)
 
 
 class _WgradSide:
@@ -1007,6 +1086,8 @@ def maxpool_bwd(dy, idx, in_shape, dx=None, accumulate=False):
 STEM_FUSE = _os.environ.get("MCAV_STEM_FUSE", "1") != "0"          # 0: bn_apply, maxpool_fwd / maxpool_bwd, bn_backward as separate passes (A/B timing)
 # the backward's second pass: 0 = pass A leaves the masked gradient in place of dy and mcav_bn_bwd_apply reads it; 1 = pass B gathers and masks again
 STEM_BWD_REGATHER = _os.environ.get("MCAV_STEM_BWD_REGATHER", "0") != "0"
+# 1: with the in-place form above, bn1's backward apply runs inside conv1's weight gradient (mcav_wgrad_desc.dy_bn_*): no dc1 in HBM.  0: mcav_bn_bwd_apply
+STEM_WGRAD_BN = _os.environ.get("MCAV_STEM_WGRAD_BN", "1") != "0"
 
 
 def stem_fusable(C):
@@ -1026,9 +1107,17 @@ def stem_bn_relu_pool_fwd(x, st):
     return y, pooled, idx
 
 
-def stem_pool_bn_backward(bn, st, dy, dpooled, idx, x, regather=None):
+def stem_pool_bn_backward_for_wgrad(bn, st, dy, dpooled, idx, x):
+    """stem_pool_bn_backward for a caller whose only reader of dx is conv1's weight gradient -> (gradient, DyBn or None) for
+    conv_wgrad(..., dy_bn=...): with STEM_WGRAD_BN and the in-place form the second pass is left to that launch (the gradient is the masked one
+    left in dy, with the pieces of the formula); otherwise (dx, None)."""
+    return stem_pool_bn_backward(bn, st, dy, dpooled, idx, x, _fold=STEM_WGRAD_BN and not STEM_BWD_REGATHER)
+
+
+def stem_pool_bn_backward(bn, st, dy, dpooled, idx, x, regather=None, _fold=None):
     """Backward of stem_bn_relu_pool_fwd for a train-mode BatchNorm -> dx (gradient at the raw conv output x).  dy: the gradient reaching the
-    activated map from elsewhere (consumed: overwritten unless regather); dpooled: the gradient at the pooled map.  Accumulates dgamma / dbeta."""
+    activated map from elsewhere (consumed: overwritten unless regather); dpooled: the gradient at the pooled map.  Accumulates dgamma / dbeta.
+    (_fold: stem_pool_bn_backward_for_wgrad's call, which returns a pair.)"""
     B, H, W, C = x.shape
     h = L.lib()
     G = st.groups
@@ -1038,6 +1127,8 @@ def stem_pool_bn_backward(bn, st, dy, dpooled, idx, x, regather=None):
     gg, gb = grad_buffer(bn.weight), grad_buffer(bn.bias)
     L.check(h.mcav_stem_pool_bn_bwd_reduce(P(dy), P(dpooled), P(idx), P(x), P(st.scale), P(st.shift), P(st.mean), P(st.invstd), B, H, W, C, G,
                                            int(not regather), P(gg), P(gb), 1, P(sums), P(ws), ws.numel(), L.stream()), "mcav_stem_pool_bn_bwd_reduce")
+    if _fold and not regather:
+        return dy, DyBn(x, bn.weight, st.mean, st.invstd, sums, G)
     dx = torch.empty_like(x)
     if regather:
         L.check(h.mcav_stem_pool_bn_bwd_apply(P(dy), P(dpooled), P(idx), P(x), P(st.scale), P(st.shift), P(bn.weight), P(st.mean), P(st.invstd),
@@ -1045,7 +1136,7 @@ def stem_pool_bn_backward(bn, st, dy, dpooled, idx, x, regather=None):
     else:
         L.check(h.mcav_bn_bwd_apply(P(dy), None, P(x), P(bn.weight), P(st.mean), P(st.invstd), P(sums), 0, B * H * W, C, P(dx), None, 0, G, L.stream()),
                 "mcav_bn_bwd_apply")
-    return dx
+    return dx if _fold is None else (dx, None)
 
 
 def act_bwd(dy, y, act, out=None, accumulate=False):

@@ -1,6 +1,7 @@
 """Forward / backward engine of the pose network (reference models/pose/pose_net.py:31-77) on NHWC tensors.
 
-cat(tgt, ref0, ref1) is packed once into a 16-channel NHWC buffer (9 real channels); seven stride-2 conv + bias + ReLU
+cat(tgt, ref0, ref1) is read by conv1's stem kernel straight from the three NCHW images (N.STEM_PLANAR; else packed once into a
+16-channel NHWC buffer, 9 real channels); seven stride-2 conv + bias + ReLU
 launches (activation fused into the conv epilogue), the 1x1 pose head, spatial mean, x 0.06.  Backward: every dgrad
 multiplies by the ReLU mask of the layer it feeds in its epilogue; stride-2 dgrads use parity-class tiles.
 """
@@ -11,6 +12,8 @@ KS = (7, 5, 3, 3, 3, 3, 3)
 
 
 def pack_inputs(tgt, refs):
+    if N.STEM_PLANAR and len(refs) == 2 and tgt.dim() == 4 and tgt.shape[1] == 3:
+        return N.PlanarImages([tgt, refs[0], refs[1]], N.PLANAR_CHANNELS, 16)      # conv1 and its weight gradient read the images themselves
     if len(refs) == 2:
         return N.nchw3_to_nhwc(N.L.dev(tgt.contiguous(), "tgt"), N.L.dev(refs[0].contiguous(), "ref"), N.L.dev(refs[1].contiguous(), "ref"), 16)
     buf = None

@@ -78,6 +78,8 @@ def _to_nhwc4(x):
     x = L.dev(x.contiguous(), "image")
     if x.shape[1] != 3:
         raise L.MCAVError("expected a 3-channel image batch [B,3,H,W]")
+    if N.STEM_PLANAR:
+        return N.PlanarImages([x], N.PLANAR_BATCH, 4)      # conv1 and its weight gradient read the image itself
     return N.nchw_to_nhwc(x, 4)
 
 
@@ -231,9 +233,12 @@ class _DispResNetPairFn(torch.autograd.Function):
             raise L.MCAVError("forward_pair: two [B,3,H,W] image batches of one shape")
         B = xa.shape[0]
         scales = mod.active_scales()
-        x4 = torch.zeros((2 * B, xa.shape[2], xa.shape[3], 4), dtype=torch.float32, device=xa.device)      # (the kernel keeps channel 3 as it finds it)
-        N.nchw_to_nhwc(xa, 4, x4[:B])                  # both passes into ONE stacked NHWC4 buffer (no concatenation pass)
-        N.nchw_to_nhwc(xb, 4, x4[B:])
+        if N.STEM_PLANAR:
+            x4 = N.PlanarImages([xa, xb], N.PLANAR_BATCH, 4)      # the stem reads both images where they are: image b of the stack is xa[b] or xb[b - B]
+        else:
+            x4 = torch.zeros((2 * B, xa.shape[2], xa.shape[3], 4), dtype=torch.float32, device=xa.device)      # (the kernel keeps channel 3 as it finds it)
+            N.nchw_to_nhwc(xa, 4, x4[:B])              # both passes into ONE stacked NHWC4 buffer (no concatenation pass)
+            N.nchw_to_nhwc(xb, 4, x4[B:])
         feats, esv = E.encoder_forward(mod.encoder.encoder, x4, mod.training, groups=2)
         disps, dsv = E.decoder_forward(mod.decoder, feats, scales)
         ctx.mod, ctx.esv, ctx.dsv, ctx.scales = mod, esv, dsv, scales
