@@ -314,6 +314,45 @@ int mcav_pseudo_lidar_project(const float* depth, int rows, int cols, const doub
                               double* cloud, size_t capacity_points, unsigned* count_out_dev, void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* A batch of network outputs -> float32 pseudo-LiDAR clouds (x, y, z, i as KITTI .bin files and sensor_msgs/PointCloud2 hold them), with
+ * the resize to the calibration's resolution inside.  The definition is tests/pl_batch_ref.py.  For image b with true size
+ * (Hb, Wb) = sizes[b] inside the padded (Hg, Wg), P = P[b] (3x4) and T = T[b] (4x4 velodyne -> camera), at pixel (r, c), r < Hb, c < Wb:
+ *   v       = the [h, w] plane m[b] resized to (Hb, Wb) as mcav_eval_depth resizes the disparity (bilinear, half-pixel centres, edge
+ *             clamping, csrc/eval_math.h bilinear_sample); m[b][r][c] itself when (h, w) == (Hb, Wb) (no taps, no 0 * inf)
+ *   d       = 1 / (10 v + 0.01) * scale, float32, every operation rounded (the depth mcav_eval_depth scores); with
+ *             MCAV_PLB_INPUT_DEPTH d = v * scale
+ *   point   = mcav_pseudo_lidar_project's float64 sequence: x = ((c - cu) d) / fu + bx, y likewise,
+ *             q_j = ((x ti[j][0] + y ti[j][1]) + d ti[j][2]) + ti[j][3], with cu, cv, fu, fv, bx, by and ti = [R' | -R' t] formed from P
+ *             and T exactly as there (on the device here)
+ *   keep    q0 >= 0 && q2 < max_height && d <= max_depth (a NaN fails; max_depth = +inf switches that cut off)
+ *   row     = (float32(q0), float32(q1), float32(q2), i), i = 0 or the plane intensity[b] resized as m[b]
+ * Dense form (elev == azim == NULL, n_beams == n_azimuth == 0): the rows of the kept pixels in (image, row-major pixel) order; with
+ *   sparsity = k > 0 every k-th kept pixel of each image, the rank starting at 0 in every image (the reference's cloud[0::k] per frame).
+ * Beam form: elev [n_beams + 1] holds tan(e) |tan(e)| at the beam edges, azim [n_azimuth + 1] tan(phi) at the azimuth edges, both float64,
+ *   finite and strictly increasing (mcav_pl_beam_tables_check tells, on HOST copies; MCAV_E_INVALID otherwise).  A kept pixel with q0 > 0
+ *   has s = q2 |q2| / (q0 q0 + q1 q1) and a = q1 / q0; its beam is the k with elev[k] <= s < elev[k+1], its azimuth bin likewise from a;
+ *   outside either table, or NaN: dropped.  Per (image, beam, azimuth) cell the pixel with the smallest float32((q0 q0 + q1 q1) + q2 q2)
+ *   wins, ties to the lowest pixel index; the winners' rows in (image, beam, azimuth) order.  sparsity is ignored.
+ * offsets[b] .. offsets[b+1] is image b's slice of cloud (offsets[B] = the number of rows).  Rows at or beyond capacity_points are not
+ * written; offsets stay exact.
+ * m, intensity (or NULL): device [B, h, w] float32; sizes: device int [B, 2]; calib: device [B, 28] doubles, P (12, row-major) then T (16);
+ * elev, azim: device; cloud: device [capacity_points, 4] float32, 16-byte aligned; offsets: device int [B + 1].
+ * Sizes are clamped to (Hg, Wg) in the kernels, so no value reads or writes out of bounds.  Integer atomicMin only: bit-identical from run
+ * to run and for any launch order.  No host synchronisation, allocation or host copy: the call can be captured.  Dense: 4 launches
+ * (calibration, count, scan, scatter); beams: a memset and 5 launches (calibration, bin, count, scan, scatter).
+ * Workspace (mcav_pl_batch_workspace_bytes, each piece rounded up to 256 bytes): B * 120 bytes of calibration,
+ * 4 * (B * max(ceil(Hg Wg / 256), ceil(n_beams n_azimuth / 256)) + 1) of counts, 8 * B * n_beams * n_azimuth of cells.  No zero-fill needed.
+ * Returns MCAV_E_INVALID for a null required pointer, a non-positive size, B * Hg * Wg, B * h * w or B * n_beams * n_azimuth >= 2^31,
+ * sparsity < 0, only one of elev / azim / n_beams / n_azimuth given, a NaN scalar, a misaligned cloud or unknown flag bits, and
+ * MCAV_E_WORKSPACE for a workspace below mcav_pl_batch_workspace_bytes (which is 0 for sizes it refuses); nothing is launched then. */
+#define MCAV_PLB_INPUT_DEPTH 1
+size_t mcav_pl_batch_workspace_bytes(int B, int Hg, int Wg, int n_beams, int n_azimuth);
+int mcav_pl_beam_tables_check(const double* elev_host, int n_beams, const double* azim_host, int n_azimuth);
+int mcav_pl_batch_project(const float* m, int B, int h, int w, int Hg, int Wg, const int* sizes, const double* calib,
+                          const float* intensity, const double* elev, const double* azim, int n_beams, int n_azimuth,
+                          float scale, double max_height, double max_depth, int sparsity, int flags, float* cloud,
+                          size_t capacity_points, int* offsets, void* workspace, size_t workspace_bytes, void* stream);
+
 /* KITTI Eigen ground truth from raw Velodyne scans (monodepth2 kitti_utils.generate_depth_map), the forward direction of the projection
  * above: scan -> sparse depth map, per image of a batch.  The definition is tests/velo_ref.py; for image b with points p = (x, y, z, r)
  * (float32, as stored in the .bin file; r is never read), P = P[b] (3x4 velodyne -> image, float64) and true size (Hb, Wb) = sizes[b]:

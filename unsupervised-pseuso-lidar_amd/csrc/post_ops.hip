@@ -106,23 +106,14 @@ __global__ __launch_bounds__(256) void depth_metrics_finalize_kernel(const doubl
 }
 
 // ---------------------------------------------------------------------------------------------- pseudo-LiDAR
-struct PLCalib {
-    double cu, cv, fu, fv, bx, by;       // from P_rect_02 (PseudoLiDAR.py:78-83)
-    double ti[3][4];                     // rows 0..2 of inverse_rigid_trans(T) (PseudoLiDAR.py:39-46); its 4th row is zero
-};
+}  // namespace mcav
+
+#include "pl_math.h"                     // PLCalib, pl_calib, pl_point; float64 without contraction from here on
+#pragma clang fp contract(off)
+
+namespace mcav {
 
 constexpr int PL_THREADS = 256;
-
-#pragma clang fp contract(off)           // the reference is numpy float64: keep mul / add separate as it does
-__device__ __forceinline__ bool pl_point(const float* depth, int cols, const PLCalib& c, size_t i, double (&q)[3]) {
-    const int r = (int)(i / cols), cc = (int)(i - (size_t)r * cols);
-    const double d = (double)depth[i];
-    const double x = (((double)cc - c.cu) * d) / c.fu + c.bx;
-    const double y = (((double)r - c.cv) * d) / c.fv + c.by;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) q[j] = ((x * c.ti[j][0] + y * c.ti[j][1]) + d * c.ti[j][2]) + c.ti[j][3];
-    return q[0] >= 0.0 && q[2] < 1.0;
-}
 
 __global__ __launch_bounds__(PL_THREADS) void pl_count_kernel(const float* depth, int cols, size_t n, PLCalib c, unsigned* counts) {
     __shared__ unsigned wsum[PL_THREADS / 64];
@@ -220,14 +211,7 @@ MCAV_EXPORT int mcav_pseudo_lidar_project(const float* depth, int rows, int cols
     const double* T = T_velo_to_cam;
     const double* P = P_rect;
     PLCalib c;
-    c.cu = P[2]; c.cv = P[4 + 2]; c.fu = P[0]; c.fv = P[4 + 1];
-    c.bx = P[3] / (-c.fu); c.by = P[4 + 3] / (-c.fv);
-    for (int i = 0; i < 3; ++i) {                         // inverse_rigid_trans: [R' | -R' t]
-        for (int j = 0; j < 3; ++j) c.ti[i][j] = T[j * 4 + i];
-        double acc = 0.0;
-        for (int j = 0; j < 3; ++j) acc += -T[j * 4 + i] * T[j * 4 + 3];
-        c.ti[i][3] = acc;
-    }
+    pl_calib(T, P, c);
     const size_t n = (size_t)rows * cols;
     const int nblocks = (int)((n + PL_THREADS - 1) / PL_THREADS);
     unsigned* counts = reinterpret_cast<unsigned*>(workspace);

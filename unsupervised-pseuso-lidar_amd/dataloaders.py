@@ -328,10 +328,13 @@ class KittiDataset(Dataset):
         if self.velodyne_gt and not self.raw:
             raise ValueError("datasets.groundtruth: velodyne builds the maps on the GPU (PrefetchLoader); it takes no host transforms")
         self.stereo = stereo_from_config(config)     # loss.stereo: each sample also carries its target's image_03 twin and the baseline
+        # opt-in: each sample also carries its date's P_rect_02 and velodyne -> camera transform, its native size and its path (inference.py)
+        self.calibration = bool(ds.get('calibration', False))
         self.samples = []
         self._calib = {}
         self._baseline = {}
         self._velo = {}
+        self._pl_calib = {}
 
     def __len__(self):
         return len(self.samples)
@@ -399,6 +402,17 @@ class KittiDataset(Dataset):
         P, hw = self._velo[d]
         return P.copy(), hw
 
+    def pl_calib_of(self, image_path):
+        """datasets.calibration: (P_rect_02 [3,4], T velodyne -> camera [4,4] = [R | T; 0 0 0 1]) of the drive's date directory, float64, as
+        pseudo_lidar.PseudoLiDAR reads them; cached per directory."""
+        d = find_calib_dir(self.resolve(image_path))
+        if d not in self._pl_calib:
+            v2c = read_calib_file(d + "calib_velo_to_cam.txt")
+            T = np.vstack([np.concatenate((v2c["R"].reshape(3, 3), v2c["T"].reshape(3, 1)), axis=1), [0.0, 0.0, 0.0, 1.0]])
+            self._pl_calib[d] = (read_calib_file(d + "calib_cam_to_cam.txt")["P_rect_02"].reshape(3, 4).copy(), T)
+        P, T = self._pl_calib[d]
+        return P.copy(), T.copy()
+
     def load_img(self, path, gt=False):
         """-> (image, original height, original width).  raw mode: uint8 [H0, W0, 3] tensor (the GPU runs the chain); ground truth: the
         depth PNG as float32, resized with Pillow's bilinear filter on mode 'F' (what ToPILImage + Resize do to a float map), [1, h, w];
@@ -436,6 +450,11 @@ class KittiDataset(Dataset):
         if self.stereo:
             ret['stereo'] = self.load_img(sample['stereo'])[0]
             ret['stereo_baseline'] = torch.tensor(sample['stereo_baseline'], dtype=torch.float32)
+        if self.calibration:
+            P, T = self.pl_calib_of(sample['tgt'])
+            ret['P_rect'], ret['T_velo_cam'] = torch.from_numpy(P), torch.from_numpy(T)
+            ret['native_size'] = torch.tensor((og_h, og_w), dtype=torch.int32)
+            ret['path'] = sample['tgt']
         if self.velodyne_gt:
             # the raw scan, unfiltered: PrefetchLoader projects the batch's scans on the GPU
             if tuple(sample['velodyne_size']) != (og_h, og_w):
@@ -496,7 +515,8 @@ class PrefetchLoader:
     warp samples pixel centres 0..w-1) are mirrored.  Call set_epoch(epoch) before each pass: the records are drawn for (seed, rank, epoch).
     Stereo samples (loss.stereo): the target's image_03 twin runs through the same plain transform as a fourth frame set (no network sees
     it, so never jittered) -> 'stereo' [B,3,h,w], and 'stereo_baseline' [B] float32 on the device; a flipped sample's stereo frame is
-    mirrored and its baseline negated (the stereo camera is then on the other side)."""
+    mirrored and its baseline negated (the stereo camera is then on the other side).
+    datasets.calibration: 'P_rect' [B,3,4] and 'T_velo_cam' [B,4,4] float64, 'native_size' [B,2] int32 (all host) and 'path' (B strings)."""
 
     def __init__(self, loader, img_height, img_width, device="cuda", depth=2, native_groundtruth=False, augment=None):
         dev = torch.device(device)
@@ -557,6 +577,13 @@ class PrefetchLoader:
             K = K.to(self.device, non_blocking=True)
             if rng is not None:
                 extra['tgt_aug'], extra['ref_imgs_aug'] = out_aug[:B], [out_aug[B:2 * B], out_aug[2 * B:]]
+            if 'P_rect' in samples[0]:
+                # datasets.calibration: host tensors (PseudoLiDAR.project_batch builds its device table from them); they describe the
+                # unflipped image
+                extra['P_rect'] = torch.stack([s['P_rect'] for s in samples])
+                extra['T_velo_cam'] = torch.stack([s['T_velo_cam'] for s in samples])
+                extra['native_size'] = torch.stack([s['native_size'] for s in samples])
+                extra['path'] = [s['path'] for s in samples]
             if 'velodyne' in samples[0]:
                 # datasets.groundtruth: velodyne -- the batch's scans in one pinned buffer, one copy, the maps projected on this stream
                 scans = [s['velodyne'] for s in samples]

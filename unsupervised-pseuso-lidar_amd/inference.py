@@ -1,0 +1,124 @@
+"""inference.py -- from a checkpoint and a KITTI split to pseudo-LiDAR clouds on disk (the reference's inference.py stops at a plot).
+
+    inf = Inference(config, checkpoint="pretrained/model.pth")
+    disp = inf.disparity(images)                       # [B, 1, h, w], evaluation mode, no gradients
+    cb = inf.clouds(samples, beams=beam_tables())      # a pseudo_lidar.CloudBatch for one loader batch
+    n = inf.export("out")                              # out/<date>/<drive>/pseudo_velodyne/data/<frame>.bin for every frame of the split
+
+    python inference.py --config C --checkpoint X --out DIR [--beams NB NA] [--scale S] [--max-depth D]
+
+Only the depth network is built (as Trainer.load_from_config builds it); no pose net, no optimiser.  The loader runs with
+datasets.calibration, so every batch carries its frames' P_rect_02, velodyne -> camera transform, native size and path; the clouds are
+made by PseudoLiDAR.project_batch at the native resolution (one kernel sequence and, in export, one read-back per batch)."""
+import argparse
+import importlib
+import os
+from inspect import getmembers, isclass
+
+import numpy as np
+import torch
+import yaml
+
+from pseudo_lidar import PseudoLiDAR, beam_tables
+
+
+class Inference:
+    def __init__(self, config, checkpoint=None, dataset=None):
+        if not torch.cuda.is_available():
+            raise RuntimeError("Inference: the MI355X path needs a GPU (there is no CPU fallback)")
+        self.config = config
+        self.device = torch.device('cuda', torch.cuda.current_device())
+        self.depth_model = self.load_from_config(config)
+        if checkpoint is not None:
+            state = torch.load(checkpoint, map_location=self.device)
+            self.depth_model.load_state_dict(state['dpth_mdl_state_dict'])
+        self.depth_model.eval()
+        self.dataset = dataset
+        self.projector = PseudoLiDAR.from_matrices(np.eye(4), np.eye(3, 4), 0)     # every call brings its frames' own calibration
+
+    def load_from_config(self, config):
+        """The depth model of Trainer.load_from_config"""
+        spec = config['model']['depth']
+        module = importlib.import_module('models.depth.' + spec['file'])
+        model = dict(getmembers(module, isclass)).get(spec['name'])
+        if model is None:
+            raise ValueError("config: no class %s in models.depth.%s" % (spec['name'], spec['file']))
+        scales = spec.get('scales')
+        if scales is None:
+            return model().to(self.device)
+        import inspect
+        if 'scales' not in inspect.signature(model.__init__).parameters:
+            raise ValueError("config model.depth.scales: %s takes no `scales` argument" % spec['name'])
+        return model(scales=int(scales)).to(self.device)
+
+    @torch.no_grad()
+    def disparity(self, images):
+        """images [B, 3, h, w] (normalised, as the loader gives 'tgt') -> the sigmoid disparity [B, 1, h, w]"""
+        self.depth_model.eval()
+        out = self.depth_model(images.to(self.device, non_blocking=True))
+        return out[0] if isinstance(out, (list, tuple)) else out
+
+    @torch.no_grad()
+    def clouds(self, samples, **kw):
+        """One batch of a datasets.calibration loader -> CloudBatch.  kw: PseudoLiDAR.project_batch's (scale, max_height, max_depth, beams,
+        intensity, out)."""
+        for key in ('P_rect', 'T_velo_cam', 'native_size'):
+            if key not in samples:
+                raise ValueError("Inference.clouds: the batch has no %r; build the dataset with datasets.calibration: true" % key)
+        return self.projector.project_batch(self.disparity(samples['tgt']), sizes=samples['native_size'], P=samples['P_rect'],
+                                            T=samples['T_velo_cam'], **kw)
+
+    def loader(self):
+        """Every frame of the split, in order, with its calibration"""
+        from dataloaders import PrefetchLoader, UnSupKittiDataset, raw_collate
+        if self.dataset is None:
+            cfg = dict(self.config, datasets=dict(self.config['datasets'], calibration=True))
+            self.dataset = UnSupKittiDataset(cfg, transforms=None)
+        if not getattr(self.dataset, "calibration", False):
+            raise ValueError("Inference: the dataset must be built with datasets.calibration: true")
+        act = self.config['action']
+        dl = torch.utils.data.DataLoader(self.dataset, batch_size=act['batch_size'], shuffle=False, num_workers=act.get('num_workers', 0),
+                                         drop_last=False, collate_fn=raw_collate)
+        return PrefetchLoader(dl, self.dataset.img_height, self.dataset.img_width, self.device,
+                              native_groundtruth=bool(getattr(self.dataset, "native_gt", False)))
+
+    @staticmethod
+    def cloud_path(out_dir, image_path):
+        """<out_dir>/<date>/<drive>/pseudo_velodyne/data/<frame>.bin of .../<date>/<drive>/image_02/data/<frame>.png"""
+        parts = os.path.normpath(image_path).split(os.sep)
+        if len(parts) < 5 or parts[-2] != "data":
+            raise ValueError("Inference.export: %r is not a KITTI raw frame (<date>/<drive>/image_02/data/<frame>.png)" % image_path)
+        return os.path.join(out_dir, parts[-5], parts[-4], "pseudo_velodyne", "data", os.path.splitext(parts[-1])[0] + ".bin")
+
+    def export(self, out_dir, loader=None, **kw):
+        """Writes one KITTI .bin (float32 x y z i) per frame of the split and returns the number of files."""
+        n = 0
+        for samples in (self.loader() if loader is None else loader):
+            paths = [self.cloud_path(out_dir, p) for p in samples['path']]
+            for p in paths:
+                os.makedirs(os.path.dirname(p), exist_ok=True)
+            self.clouds(samples, **kw).save_bin(paths)
+            n += len(paths)
+        return n
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="checkpoint + KITTI split -> pseudo-LiDAR .bin clouds")
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--checkpoint", required=True)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--beams", nargs=2, type=int, metavar=("NB", "NA"), help="one return per cell of an NB x NA beam grid (default: dense)")
+    ap.add_argument("--scale", type=float, default=1.0, help="multiplies the depth (pred_depth_scale_factor)")
+    ap.add_argument("--max-depth", type=float, default=None)
+    args = ap.parse_args(argv)
+    with open(args.config) as f:
+        config = yaml.full_load(f)
+    kw = dict(scale=args.scale, max_depth=args.max_depth)
+    if args.beams:
+        kw["beams"] = beam_tables(args.beams[0], args.beams[1])
+    n = Inference(config, args.checkpoint).export(args.out, **kw)
+    print("wrote %d clouds under %s" % (n, args.out))
+
+
+if __name__ == "__main__":
+    main()

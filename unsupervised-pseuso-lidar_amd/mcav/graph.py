@@ -175,6 +175,11 @@ class GraphedStep:
             # device tables exist before it (building one is a host -> device copy, which a capturing stream refuses)
             if self.sync is not None:
                 N.GRADS_READY = lambda params: None
+            # Modules that only the cyclic collector can free (an earlier Trainer) go NOW, as torch.cuda.graph does before it captures: if
+            # they went between warm-up and capture, their entries would drop out of the packed-filter registry (nn.PackRegistry) and its
+            # table would be rebuilt under capture, by the same kind of host -> device copy.
+            import gc
+            gc.collect()
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):

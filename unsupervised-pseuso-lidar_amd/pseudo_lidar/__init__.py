@@ -1,1 +1,1 @@
-from .PseudoLiDAR import PseudoLiDAR  # noqa: F401
+from .PseudoLiDAR import BeamTables, CloudBatch, PseudoLiDAR, beam_tables  # noqa: F401
