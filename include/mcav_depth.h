@@ -302,6 +302,13 @@ int mcav_eval_depth(const float* gt, const float* disp, int B, int Hg, int Wg, i
                     const int* sizes, const int* boxes,
                     float min_depth, float max_depth, float scale, int flags,
                     float* rows, void* workspace, size_t workspace_bytes, void* stream);
+/* mcav_eval_depth with a per-image scale on the device: pred = 1 / (10 up + 0.01) * s_b, s_b = scale * scales[b] formed once in float32
+ * (scales: device [B], e.g. column 0 of mcav_ground_scale's rows; NULL = mcav_eval_depth, bit for bit).  The optional median scaling and
+ * everything else as there; rows[:, 10] stays the median ratio (1 without it).  A NaN s_b makes that image's metrics NaN. */
+int mcav_eval_depth_scaled(const float* gt, const float* disp, int B, int Hg, int Wg, int h, int w,
+                           const int* sizes, const int* boxes,
+                           float min_depth, float max_depth, float scale, const float* scales, int flags,
+                           float* rows, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Depth image -> pseudo-LiDAR cloud, reference pseudo-lidar/utils/PseudoLiDAR.py:69-110 (project_PL) with :39-46
  * (inverse_rigid_trans): un-project with P_rect_02, transform into the velodyne frame, keep x >= 0 and z < 1 m, keep every
@@ -352,6 +359,46 @@ int mcav_pl_batch_project(const float* m, int B, int h, int w, int Hg, int Wg, c
                           const float* intensity, const double* elev, const double* azim, int n_beams, int n_azimuth,
                           float scale, double max_height, double max_depth, int sparsity, int flags, float* cloud,
                           size_t capacity_points, int* offsets, void* workspace, size_t workspace_bytes, void* stream);
+/* mcav_pl_batch_project with a per-image scale on the device: d = 1 / (10 v + 0.01) * s_b (or v * s_b), s_b = scale * scales[b] formed
+ * once in float32 (scales: device [B]; NULL = mcav_pl_batch_project, bit for bit).  An image whose s_b is not finite or not positive keeps
+ * no pixel (offsets stay exact): a fallback of NaN from mcav_ground_scale yields an empty cloud. */
+int mcav_pl_batch_project_scaled(const float* m, int B, int h, int w, int Hg, int Wg, const int* sizes, const double* calib,
+                                 const float* intensity, const double* elev, const double* azim, int n_beams, int n_azimuth,
+                                 float scale, const float* scales, double max_height, double max_depth, int sparsity, int flags,
+                                 float* cloud, size_t capacity_points, int* offsets, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
+/* Metric scale of a monocular prediction from the ground plane (DNet's dense geometrical constraint, Xue et al., IROS 2020): per image, a
+ * surface normal per pixel from the back-projected depth, the pixels whose normal points along the camera's "down" axis, and
+ * scale = camera_height / median(height of those pixels above the plane through the camera centre).  No ground truth is read.
+ * The definition is tests/ground_scale_ref.py; per-pixel math: csrc/ground_math.h.  For image b of m [B, h, w] with true size
+ * (Hb, Wb) = sizes[b] and P = P[b] (fu = P00, fv = P11, cu = P02, cv = P12), float32 with every operation rounded on its own:
+ *   rays    xn[c] = float32((((c + 0.5) Wb) / w - 0.5 - cu) / fu), the inner arithmetic in float64 in that order; yn[r] alike from Hb, h,
+ *           cv, fv: the native pixel a network pixel centre maps to under mcav_eval_depth's half-pixel resize
+ *   depth   d = 1 / (10 v + 0.01); with MCAV_GS_INPUT_DEPTH d = v.           point  Pt = (xn[c] d, yn[r] d, d)
+ *   normal  for an interior pixel (1 <= r <= h-2, 1 <= c <= w-2) inside the box: e_k = Pt(neighbour k) - Pt(centre) for R, D, L, U, DR, DL,
+ *           UL, UR; the cross products (R,D) (D,L) (L,U) (U,R) (DR,DL) (DL,UL) (UL,UR) (UR,DR), cx = a.y b.z - a.z b.y and so on,
+ *           len = sqrt((cx cx + cy cy) + cz cz), u = c / len; acc = the eight u summed in that order from +0; L = |acc|, n = acc / L
+ *   height  hgt = (n.x X + n.y Y) + n.z Z of the centre
+ *   ground  every len and L finite and > 0, n.y >= cos_max, hgt finite and > 0 (a NaN fails every test)
+ *   rows[b] = { scale, med, count, status }: count ground pixels, med their exact median as np.median on float32 (NaN without any),
+ *           count >= min_ground: scale = camera_height / med, status 1; otherwise scale = fallback, status 0.
+ * m: device [B, h, w]; sizes: device int [B, 2]; calib: device [B, 28] doubles as mcav_pl_batch_project takes them (only P is read);
+ * boxes: device int [B, 4] (y0, y1, x0, x1) in network pixels, half-open, clamped in the kernel, or NULL (the whole interior);
+ * rows: device [B, 4]; mask_out: device [B, h, w] bytes, 1 on ground pixels, or NULL.
+ * Two launches: a pixel pass (one workgroup per 8 x 32 tile of the image's interior, the tile's points and a one-pixel halo in LDS) that
+ * leaves a key per interior pixel -- the bits of hgt, which order positive floats, or 0xFFFFFFFF -- and one workgroup per image that
+ * selects both median ranks exactly from those keys over 11 + 11 + 10 bits.  LDS integer atomics only; rows and mask are bit-identical
+ * from run to run.  No host synchronisation, allocation or copy: the call can be captured.
+ * Workspace (mcav_ground_scale_workspace_bytes): 4 * B * (h - 2) * (w - 2) bytes, rounded up to 256, 4-byte aligned; no zero-fill.
+ * Returns MCAV_E_INVALID for a null required pointer, h < 3, w < 3, B <= 0, B * h * w >= 2^31, a camera_height that is not finite and
+ * positive, cos_max outside (0, 1], min_ground < 1, unknown flag bits or a workspace address that is no multiple of 4, MCAV_E_WORKSPACE
+ * for a short workspace; nothing is launched then. */
+#define MCAV_GS_INPUT_DEPTH 1
+size_t mcav_ground_scale_workspace_bytes(int B, int h, int w);
+int mcav_ground_scale(const float* m, int B, int h, int w, const int* sizes, const double* calib, const int* boxes, float camera_height,
+                      float cos_max, int min_ground, float fallback, int flags, float* rows, unsigned char* mask_out, void* workspace,
+                      size_t workspace_bytes, void* stream);
 
 /* KITTI Eigen ground truth from raw Velodyne scans (monodepth2 kitti_utils.generate_depth_map), the forward direction of the projection
  * above: scan -> sparse depth map, per image of a batch.  The definition is tests/velo_ref.py; for image b with points p = (x, y, z, r)

@@ -54,6 +54,7 @@ struct EVArgs {
     const int* boxes;          // [B,4]
     int B, Hg, Wg, h, w;
     float min_depth, max_depth, scale;
+    const float* scales;       // [B] or null: the image's scale is scale * scales[b]
     int flags;
     float* rows;               // [B,11]
     unsigned* meta;            // [B][2]: number of masked pixels, NaN flag of pred
@@ -67,9 +68,12 @@ struct EVArgs {
 __device__ __forceinline__ size_t ev_plane(const EVArgs& a) { return (size_t)a.Hg * a.Wg; }
 
 // The image's disparity -> depth at ground-truth pixel (y, x), before any ratio
-__device__ __forceinline__ float ev_pred(const EVArgs& a, const float* dp, float sy, float sx, int y, int x) {
-    return ev::disp_depth(ev::bilinear_sample(dp, a.h, a.w, sy, sx, y, x), a.scale);
+__device__ __forceinline__ float ev_pred(const EVArgs& a, const float* dp, float sy, float sx, int y, int x, float scale) {
+    return ev::disp_depth(ev::bilinear_sample(dp, a.h, a.w, sy, sx, y, x), scale);
 }
+
+// The scale of image b: the caller's, times the image's own where a table came (mcav_eval_depth_scaled), formed once in float32
+__device__ __forceinline__ float ev_image_scale(const EVArgs& a, int b) { return a.scales ? ev::mul_rn(a.scale, a.scales[b]) : a.scale; }
 
 __device__ __forceinline__ void ev_axis_scales(const EVArgs& a, int b, float& sy, float& sx) {
     const int Hb = min(max(a.sizes[2 * b], 1), a.Hg), Wb = min(max(a.sizes[2 * b + 1], 1), a.Wg);
@@ -105,6 +109,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_gather_kernel(EVArgs a) {
     if (start >= nbox) return;                         // uniform over the workgroup
     float sy, sx;
     ev_axis_scales(a, b, sy, sx);
+    const float scale = ev_image_scale(a, b);
     const size_t plane = ev_plane(a);
     const float* gp = a.gt + (size_t)b * plane;
     const float* dp = a.disp + (size_t)b * a.h * a.w;
@@ -120,7 +125,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_gather_kernel(EVArgs a) {
         const int y = bx.y0 + q / bw, x = bx.x0 + q % bw;
         const float g = in ? gp[(size_t)y * a.Wg + x] : 0.0f;
         const bool m = in && g > a.min_depth && g < a.max_depth;
-        const float p = m ? ev_pred(a, dp, sy, sx, y, x) : 0.0f;
+        const float p = m ? ev_pred(a, dp, sy, sx, y, x, scale) : 0.0f;
         nan_seen |= m && p != p;
         bal[k] = __ballot(m);
         cnt += (unsigned)__popcll(bal[k]);
@@ -258,7 +263,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_metrics_kernel(EVArgs a) {
     if (start < nbox) {                                // uniform over the workgroup
         float sy, sx;
         ev_axis_scales(a, b, sy, sx);
-        const float ratio = ev_ratio(a, b);
+        const float ratio = ev_ratio(a, b), scale = ev_image_scale(a, b);
         const float* gp = a.gt + (size_t)b * ev_plane(a);
         const float* dp = a.disp + (size_t)b * a.h * a.w;
         for (int k = 0; k < EV_PPT; ++k) {
@@ -267,7 +272,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_metrics_kernel(EVArgs a) {
             const int y = bx.y0 + i / bw, x = bx.x0 + i % bw;
             const float g = gp[(size_t)y * a.Wg + x];
             if (!(g > a.min_depth && g < a.max_depth)) continue;
-            float p = ev_pred(a, dp, sy, sx, y, x);
+            float p = ev_pred(a, dp, sy, sx, y, x, scale);
             if (a.flags & MCAV_EVAL_MEDIAN_SCALING) p = ev::mul_rn(p, ratio);
             ev::pixel_terms(g, ev::clip(p, a.min_depth, a.max_depth), s);
         }
@@ -337,9 +342,9 @@ MCAV_EXPORT size_t mcav_eval_depth_workspace_bytes(int B, int Hg, int Wg) {
     return ev_layout(B, Hg, Wg).total;
 }
 
-MCAV_EXPORT int mcav_eval_depth(const float* gt, const float* disp, int B, int Hg, int Wg, int h, int w, const int* sizes, const int* boxes,
-                                float min_depth, float max_depth, float scale, int flags, float* rows, void* workspace, size_t workspace_bytes,
-                                void* stream) {
+MCAV_EXPORT int mcav_eval_depth_scaled(const float* gt, const float* disp, int B, int Hg, int Wg, int h, int w, const int* sizes,
+                                       const int* boxes, float min_depth, float max_depth, float scale, const float* scales, int flags,
+                                       float* rows, void* workspace, size_t workspace_bytes, void* stream) {
     if (!gt || !disp || !sizes || !boxes || !rows || !workspace) return MCAV_E_INVALID;
     if (!ev_shape_ok(B, Hg, Wg, h, w)) return MCAV_E_INVALID;
     if (flags & ~MCAV_EVAL_MEDIAN_SCALING) return MCAV_E_INVALID;
@@ -350,7 +355,7 @@ MCAV_EXPORT int mcav_eval_depth(const float* gt, const float* disp, int B, int H
     EVArgs a = {};
     a.gt = gt; a.disp = disp; a.sizes = sizes; a.boxes = boxes;
     a.B = B; a.Hg = Hg; a.Wg = Wg; a.h = h; a.w = w;
-    a.min_depth = min_depth; a.max_depth = max_depth; a.scale = scale; a.flags = flags;
+    a.min_depth = min_depth; a.max_depth = max_depth; a.scale = scale; a.scales = scales; a.flags = flags;
     a.rows = rows;
     a.meta = reinterpret_cast<unsigned*>(ws + l.meta_off);
     a.state = reinterpret_cast<unsigned*>(ws + l.state_off);
@@ -372,4 +377,11 @@ MCAV_EXPORT int mcav_eval_depth(const float* gt, const float* disp, int B, int H
     timed_launch(eval_metrics_kernel, dim3(l.G, B), dim3(EV_THREADS), 0, s, a);
     timed_launch(eval_finalize_kernel, dim3(B), dim3(EV_THREADS), 0, s, a);
     return launch_status();
+}
+
+MCAV_EXPORT int mcav_eval_depth(const float* gt, const float* disp, int B, int Hg, int Wg, int h, int w, const int* sizes, const int* boxes,
+                                float min_depth, float max_depth, float scale, int flags, float* rows, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    return mcav_eval_depth_scaled(gt, disp, B, Hg, Wg, h, w, sizes, boxes, min_depth, max_depth, scale, nullptr, flags, rows, workspace,
+                                  workspace_bytes, stream);
 }

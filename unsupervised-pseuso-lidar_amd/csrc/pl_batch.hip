@@ -26,6 +26,7 @@ struct Args {
     int h, w, Hg, Wg, nb, na;
     int per_image;                       // blocks per image of the pixel passes
     float scale;
+    const float* scales;                 // [B] or null: the image's scale is scale * scales[b]
     double max_height, max_depth;
     int input_depth;
 };
@@ -39,14 +40,25 @@ __global__ __launch_bounds__(THREADS) void plb_calib_kernel(const double* record
     out[b] = c;
 }
 
-// Pixel p of image b's padded grid: its depth and point.  false: outside the true image.
+// The scale of image b.  With a table (mcav_pl_batch_project_scaled) it is scale * scales[b], formed once in float32, and an image whose
+// scale is not finite and positive keeps no pixel (false).
+__device__ __forceinline__ bool image_scale(const Args& a, int b, float& s) {
+    s = a.scale;
+    if (!a.scales) return true;
+    s = mul(a.scale, a.scales[b]);
+    return s > 0.0f && s <= 3.40282346638528859812e+38f;
+}
+
+// Pixel p of image b's padded grid: its depth and point.  false: outside the true image (or an image without a usable scale).
 __device__ __forceinline__ bool pixel_point(const Args& a, int b, unsigned p, float& d, double (&q)[3], int& r, int& c) {
     if (p >= (unsigned)a.Hg * (unsigned)a.Wg) return false;
     r = (int)(p / (unsigned)a.Wg);
     c = (int)(p - (unsigned)r * (unsigned)a.Wg);
     const int Hb = min(a.sizes[2 * b], a.Hg), Wb = min(a.sizes[2 * b + 1], a.Wg);       // clamped: no read outside the plane
     if (r >= Hb || c >= Wb) return false;
-    d = depth_of(sample(a.m + (size_t)b * a.h * a.w, a.h, a.w, Hb, Wb, r, c), a.scale, a.input_depth != 0);
+    float s;
+    if (!image_scale(a, b, s)) return false;
+    d = depth_of(sample(a.m + (size_t)b * a.h * a.w, a.h, a.w, Hb, Wb, r, c), s, a.input_depth != 0);
     pl_point_at((double)d, r, c, a.calib[b], q);
     return true;
 }
@@ -225,10 +237,11 @@ MCAV_EXPORT int mcav_pl_beam_tables_check(const double* elev_host, int n_beams, 
     return plb::table_ok(elev_host, n_beams) && plb::table_ok(azim_host, n_azimuth) ? MCAV_OK : MCAV_E_INVALID;
 }
 
-MCAV_EXPORT int mcav_pl_batch_project(const float* m, int B, int h, int w, int Hg, int Wg, const int* sizes, const double* calib,
-                                      const float* intensity, const double* elev, const double* azim, int n_beams, int n_azimuth,
-                                      float scale, double max_height, double max_depth, int sparsity, int flags, float* cloud,
-                                      size_t capacity_points, int* offsets, void* workspace, size_t workspace_bytes, void* stream) {
+MCAV_EXPORT int mcav_pl_batch_project_scaled(const float* m, int B, int h, int w, int Hg, int Wg, const int* sizes, const double* calib,
+                                             const float* intensity, const double* elev, const double* azim, int n_beams, int n_azimuth,
+                                             float scale, const float* scales, double max_height, double max_depth, int sparsity, int flags,
+                                             float* cloud, size_t capacity_points, int* offsets, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
     if (!m || !sizes || !calib || !cloud || !offsets || !workspace || h <= 0 || w <= 0 || sparsity < 0) return MCAV_E_INVALID;
     if (flags & ~MCAV_PLB_INPUT_DEPTH) return MCAV_E_INVALID;
     if ((elev != nullptr) != (azim != nullptr) || (elev != nullptr) != (n_beams > 0)) return MCAV_E_INVALID;
@@ -248,7 +261,7 @@ MCAV_EXPORT int mcav_pl_batch_project(const float* m, int B, int h, int w, int H
     a.m = m; a.intensity = intensity; a.sizes = sizes; a.calib = cal; a.elev = elev; a.azim = azim;
     a.h = h; a.w = w; a.Hg = Hg; a.Wg = Wg; a.nb = n_beams; a.na = n_azimuth;
     a.per_image = l.per_image;
-    a.scale = scale; a.max_height = max_height; a.max_depth = max_depth;
+    a.scale = scale; a.scales = scales; a.max_height = max_height; a.max_depth = max_depth;
     a.input_depth = (flags & MCAV_PLB_INPUT_DEPTH) ? 1 : 0;
     plb::f32x4* out = reinterpret_cast<plb::f32x4*>(cloud);
     hipStream_t s = as_stream(stream);
@@ -269,4 +282,13 @@ MCAV_EXPORT int mcav_pl_batch_project(const float* m, int B, int h, int w, int H
     plb::plb_scan_kernel<<<1, 1024, 0, s>>>(counts, ncell, l.per_cells, B, 1u, offsets);
     plb::plb_cell_scatter_kernel<<<ncell, plb::THREADS, 0, s>>>(a, cells, l.per_cells, counts, out, capacity_points);
     return launch_status();
+}
+
+MCAV_EXPORT int mcav_pl_batch_project(const float* m, int B, int h, int w, int Hg, int Wg, const int* sizes, const double* calib,
+                                      const float* intensity, const double* elev, const double* azim, int n_beams, int n_azimuth,
+                                      float scale, double max_height, double max_depth, int sparsity, int flags, float* cloud,
+                                      size_t capacity_points, int* offsets, void* workspace, size_t workspace_bytes, void* stream) {
+    return mcav_pl_batch_project_scaled(m, B, h, w, Hg, Wg, sizes, calib, intensity, elev, azim, n_beams, n_azimuth, scale, nullptr,
+                                        max_height, max_depth, sparsity, flags, cloud, capacity_points, offsets, workspace, workspace_bytes,
+                                        stream);
 }

@@ -10,6 +10,7 @@ ground truth); the default -1 takes every element, as the reference does.
 `evaluate_depth(gt, pred, sizes, crop, ...)` is the KITTI protocol of monodepth2's evaluate_depth.py instead: per image, at the ground
 truth's own resolution, crop, depth range, per-image median scaling, metrics averaged over images (mcav_eval_depth; the definition is
 tests/eval_protocol_ref.py).  `reduce_rows` turns the per-image rows of several batches into that result with one read-back.
+`scales=` takes one scale per image on the device (mcav_eval_depth_scaled), e.g. pseudo_lidar.ground_scale's, which needs no ground truth.
 """
 import torch
 
@@ -20,6 +21,8 @@ L.register({
     "mcav_depth_metrics": (L.c_i, [L.c_p, L.c_p, L.c_sz, L.c_f, L.c_p, L.c_p, L.c_sz, L.c_p]),
     "mcav_eval_depth_workspace_bytes": (L.c_sz, [L.c_i, L.c_i, L.c_i]),
     "mcav_eval_depth": (L.c_i, [L.c_p, L.c_p] + [L.c_i] * 5 + [L.c_p, L.c_p, L.c_f, L.c_f, L.c_f, L.c_i, L.c_p, L.c_p, L.c_sz, L.c_p]),
+    "mcav_eval_depth_scaled": (L.c_i, [L.c_p, L.c_p] + [L.c_i] * 5 + [L.c_p, L.c_p, L.c_f, L.c_f, L.c_f, L.c_p, L.c_i, L.c_p, L.c_p, L.c_sz,
+                                       L.c_p]),
 })
 
 KEYS = ("silog", "abs_rel", "log10", "rms", "sq_rel", "log_rms", "d1", "d2", "d3")
@@ -64,7 +67,7 @@ def crop_box(Hb, Wb, crop):
     return box
 
 
-def eval_depth_rows(gt, pred, sizes=None, crop="garg", min_depth=1e-3, max_depth=80.0, median_scaling=True, scale=1.0):
+def eval_depth_rows(gt, pred, sizes=None, crop="garg", min_depth=1e-3, max_depth=80.0, median_scaling=True, scale=1.0, scales=None):
     """The per-image rows [B, 11] (ROW_KEYS: the nine metrics, count, ratio) on the device; no read-back.  Arguments as evaluate_depth."""
     disp = pred[0] if isinstance(pred, (list, tuple)) else pred
     gt = L.dev(gt.detach().to(torch.float32).contiguous(), "gt")
@@ -96,16 +99,26 @@ def eval_depth_rows(gt, pred, sizes=None, crop="garg", min_depth=1e-3, max_depth
     h_ = L.lib()
     ws = L.workspace(h_.mcav_eval_depth_workspace_bytes(B, Hg, Wg), dev, "eval_depth")
     flags = EVAL_MEDIAN_SCALING if median_scaling else 0
-    L.check(h_.mcav_eval_depth(L.ptr(gt), L.ptr(disp), B, Hg, Wg, h, w, L.ptr(meta), L.c_p(meta.data_ptr() + 4 * 2 * B),
-                               float(min_depth), float(max_depth), float(scale), flags, L.ptr(rows), L.ptr(ws), ws.numel(), L.stream()),
-            "mcav_eval_depth")
+    if scales is None:
+        L.check(h_.mcav_eval_depth(L.ptr(gt), L.ptr(disp), B, Hg, Wg, h, w, L.ptr(meta), L.c_p(meta.data_ptr() + 4 * 2 * B),
+                                   float(min_depth), float(max_depth), float(scale), flags, L.ptr(rows), L.ptr(ws), ws.numel(), L.stream()),
+                "mcav_eval_depth")
+        return rows
+    if not torch.is_tensor(scales) or tuple(scales.shape) != (B,):
+        raise L.MCAVError("evaluate_depth: scales must be a float32 tensor [%d] on the GPU" % B)
+    scales = L.dev(scales.detach().contiguous() if scales.is_cuda else scales, "scales")     # (a column of ground_scale's rows: packed here)
+    L.check(h_.mcav_eval_depth_scaled(L.ptr(gt), L.ptr(disp), B, Hg, Wg, h, w, L.ptr(meta), L.c_p(meta.data_ptr() + 4 * 2 * B),
+                                      float(min_depth), float(max_depth), float(scale), L.ptr(scales), flags, L.ptr(rows), L.ptr(ws),
+                                      ws.numel(), L.stream()), "mcav_eval_depth_scaled")
     return rows
 
 
-def reduce_rows(rows):
+def reduce_rows(rows, ground=None):
     """Per-image rows (one [B, 11] tensor or a list of them, e.g. one per batch) -> the protocol's result: the mean of every metric over
     the images with count > 0, 'images', the total pixel 'count', and monodepth2's scale statistics 'ratio_median' = median(ratios),
-    'ratio_std' = std(ratios / ratio_median).  The rows are joined on the device and read back once."""
+    'ratio_std' = std(ratios / ratio_median).  The rows are joined on the device and read back once.
+    ground: the rows [B, 4] of pseudo_lidar.ground_scale for the same images (or a list of them), when its scales were used: adds
+    'ground_scale_mean' and 'ground_scale_std' over the images the estimator accepted (status 1) and 'ground_fallbacks', the others."""
     import numpy as np
     if isinstance(rows, (list, tuple)):
         rows = torch.cat(list(rows)) if rows else torch.empty((0, 11))
@@ -118,15 +131,24 @@ def reduce_rows(rows):
     med = float(np.median(ratios)) if ratios.size else float("nan")
     out["ratio_median"] = med
     out["ratio_std"] = float(np.std(ratios / med)) if ratios.size else float("nan")
+    if ground is not None:
+        if isinstance(ground, (list, tuple)):
+            ground = torch.cat(list(ground)) if ground else torch.empty((0, 4))
+        g = ground.detach().cpu().numpy().astype(np.float64).reshape(-1, 4)
+        ok = g[:, 3] > 0
+        out["ground_scale_mean"] = float(np.mean(g[ok, 0])) if ok.any() else float("nan")
+        out["ground_scale_std"] = float(np.std(g[ok, 0])) if ok.any() else float("nan")
+        out["ground_fallbacks"] = int((~ok).sum())
     return out
 
 
-def evaluate_depth(gt, pred, sizes=None, crop="garg", min_depth=1e-3, max_depth=80.0, median_scaling=True, scale=1.0, per_image=False):
+def evaluate_depth(gt, pred, sizes=None, crop="garg", min_depth=1e-3, max_depth=80.0, median_scaling=True, scale=1.0, per_image=False,
+                   scales=None):
     """The KITTI depth protocol (monodepth2 evaluate_depth.py) on the GPU.
     gt: [B,1,Hg,Wg] or [B,Hg,Wg] ground-truth depth in metres (0 = no return), zero-padded to the batch's largest image; pred: the
     network's sigmoid disparity as compute_errors takes it ([B,1,h,w] / [B,h,w], or a list whose first entry it is).  sizes: the true
     (Hb, Wb) of every image (host; default: (Hg, Wg)).  crop: 'garg', 'eigen', None, an explicit (y0, y1, x0, x1) or a list of B of
-    them.  scale: monodepth2's pred_depth_scale_factor.  -> the dict of reduce_rows; with per_image=True also the [B, 11] device rows."""
-    rows = eval_depth_rows(gt, pred, sizes, crop, min_depth, max_depth, median_scaling, scale)
+    them.  scale: monodepth2's pred_depth_scale_factor; scales: a float32 tensor [B] on the GPU, one more factor per image.  -> the dict of reduce_rows; with per_image=True also the [B, 11] device rows."""
+    rows = eval_depth_rows(gt, pred, sizes, crop, min_depth, max_depth, median_scaling, scale, scales)
     out = reduce_rows(rows)
     return (out, rows) if per_image else out

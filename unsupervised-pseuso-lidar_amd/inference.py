@@ -5,7 +5,11 @@
     cb = inf.clouds(samples, beams=beam_tables())      # a pseudo_lidar.CloudBatch for one loader batch
     n = inf.export("out")                              # out/<date>/<drive>/pseudo_velodyne/data/<frame>.bin for every frame of the split
 
-    python inference.py --config C --checkpoint X --out DIR [--beams NB NA] [--scale S] [--max-depth D]
+    python inference.py --config C --checkpoint X --out DIR [--beams NB NA] [--scale S | --scale ground] [--max-depth D]
+                        [--camera-height M] [--ground-angle DEG] [--ground-min N]
+
+--scale ground gives every frame its own metric scale from its ground plane (pseudo_lidar.ground_scale: no ground truth, no stereo); a
+frame without enough ground pixels gets an empty cloud.
 
 Only the depth network is built (as Trainer.load_from_config builds it); no pose net, no optimiser.  The loader runs with
 datasets.calibration, so every batch carries its frames' P_rect_02, velodyne -> camera transform, native size and path; the clouds are
@@ -60,8 +64,8 @@ class Inference:
 
     @torch.no_grad()
     def clouds(self, samples, **kw):
-        """One batch of a datasets.calibration loader -> CloudBatch.  kw: PseudoLiDAR.project_batch's (scale, max_height, max_depth, beams,
-        intensity, out)."""
+        """One batch of a datasets.calibration loader -> CloudBatch.  kw: PseudoLiDAR.project_batch's (scale -- a number, a tensor [B] or
+        "ground" with its keywords in ground={...} --, max_height, max_depth, beams, intensity, out)."""
         for key in ('P_rect', 'T_velo_cam', 'native_size'):
             if key not in samples:
                 raise ValueError("Inference.clouds: the batch has no %r; build the dataset with datasets.calibration: true" % key)
@@ -102,18 +106,29 @@ class Inference:
         return n
 
 
+def scale_argument(text):
+    """--scale: a number or the word 'ground'"""
+    return "ground" if text.strip().lower() == "ground" else float(text)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="checkpoint + KITTI split -> pseudo-LiDAR .bin clouds")
     ap.add_argument("--config", required=True)
     ap.add_argument("--checkpoint", required=True)
     ap.add_argument("--out", required=True)
     ap.add_argument("--beams", nargs=2, type=int, metavar=("NB", "NA"), help="one return per cell of an NB x NA beam grid (default: dense)")
-    ap.add_argument("--scale", type=float, default=1.0, help="multiplies the depth (pred_depth_scale_factor)")
+    ap.add_argument("--scale", type=scale_argument, default=1.0,
+                    help="a number that multiplies the depth (pred_depth_scale_factor), or 'ground': every frame's own scale from its ground plane")
     ap.add_argument("--max-depth", type=float, default=None)
+    ap.add_argument("--camera-height", type=float, default=1.65, help="--scale ground: the camera above the road in metres")
+    ap.add_argument("--ground-angle", type=float, default=5.0, help="--scale ground: the cone around 'down' a ground normal lies in, degrees")
+    ap.add_argument("--ground-min", type=int, default=100, help="--scale ground: fewer ground pixels than this and the frame gets no cloud")
     args = ap.parse_args(argv)
     with open(args.config) as f:
         config = yaml.full_load(f)
     kw = dict(scale=args.scale, max_depth=args.max_depth)
+    if args.scale == "ground":
+        kw["ground"] = dict(camera_height=args.camera_height, max_angle_deg=args.ground_angle, min_ground=args.ground_min)
     if args.beams:
         kw["beams"] = beam_tables(args.beams[0], args.beams[1])
     n = Inference(config, args.checkpoint).export(args.out, **kw)

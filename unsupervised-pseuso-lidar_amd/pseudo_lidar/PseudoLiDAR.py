@@ -10,6 +10,11 @@ tensor: un-projection, rigid transform, the x >= 0 & z < 1 m cut and the order-p
 `CloudBatch` of float32 x, y, z, i rows (KITTI .bin / sensor_msgs/PointCloud2 layout) with the resize to the calibration's resolution
 inside, per-image calibration, and either the dense cloud or one return per (beam, azimuth) cell of a LiDAR-like grid
 (`beam_tables`).  mcav_pl_batch_project: nothing comes back to the host until `counts()`, `split()` or `save_bin()` ask for it.
+
+`ground_scale(m)` gives a monocular prediction its metric scale without ground truth (DNet's dense geometrical constraint): per image,
+camera_height / median height of the pixels whose surface normal points down (mcav_ground_scale; the definition is
+tests/ground_scale_ref.py).  `project_batch(..., scale="ground")` runs it and hands the per-image scales on, on the device;
+`project_batch(..., scale=<tensor [B]>)` takes any per-image scales.
 """
 import ctypes
 
@@ -25,9 +30,15 @@ L.register({
     "mcav_pl_beam_tables_check": (L.c_i, [L.c_p, L.c_i, L.c_p, L.c_i]),
     "mcav_pl_batch_project": (L.c_i, [L.c_p] + [L.c_i] * 5 + [L.c_p] * 5 + [L.c_i, L.c_i, L.c_f, ctypes.c_double, ctypes.c_double, L.c_i, L.c_i,
                                       L.c_p, L.c_sz, L.c_p, L.c_p, L.c_sz, L.c_p]),
+    "mcav_pl_batch_project_scaled": (L.c_i, [L.c_p] + [L.c_i] * 5 + [L.c_p] * 5 + [L.c_i, L.c_i, L.c_f, L.c_p, ctypes.c_double, ctypes.c_double,
+                                             L.c_i, L.c_i, L.c_p, L.c_sz, L.c_p, L.c_p, L.c_sz, L.c_p]),
+    "mcav_ground_scale_workspace_bytes": (L.c_sz, [L.c_i] * 3),
+    "mcav_ground_scale": (L.c_i, [L.c_p, L.c_i, L.c_i, L.c_i, L.c_p, L.c_p, L.c_p, L.c_f, L.c_f, L.c_i, L.c_f, L.c_i, L.c_p, L.c_p, L.c_p,
+                                  L.c_sz, L.c_p]),
 })
 
 PLB_INPUT_DEPTH = 1                            # include/mcav_depth.h MCAV_PLB_INPUT_DEPTH
+GS_INPUT_DEPTH = 1                             # include/mcav_depth.h MCAV_GS_INPUT_DEPTH
 
 
 class BeamTables:
@@ -73,6 +84,7 @@ class CloudBatch:
         self.offsets = torch.zeros(int(batch) + 1, dtype=torch.int32, device=device)
         self._host = None
         self._meta_bytes, self._meta, self._ws = None, None, None       # project_batch's calibration table and workspace
+        self.ground, self._packed, self._scales = None, None, None      # scale="ground": the estimate, its scales packed; the [B] scales in use
 
     def __len__(self):
         return self.offsets.numel() - 1
@@ -99,6 +111,98 @@ class CloudBatch:
         host = self.points[:int(o[-1])].cpu().numpy()
         for b, path in enumerate(paths):
             host[int(o[b]):int(o[b + 1])].tofile(path)
+
+
+def _plane(m, what):
+    """[B, h, w] or [B, 1, h, w] float32 on the GPU -> [B, h, w], contiguous"""
+    if not torch.is_tensor(m):
+        raise L.MCAVError("%s: m must be a tensor on the GPU" % what)
+    if m.dim() == 4 and m.shape[1] == 1:
+        m = m[:, 0]
+    if m.dim() != 3:
+        raise L.MCAVError("%s: m must be [B, h, w] or [B, 1, h, w], got %s" % (what, tuple(m.shape)))
+    return L.dev(m.contiguous() if m.is_cuda else m, "m")
+
+
+def _sizes(sizes, B, h, w, what):
+    sz = np.asarray([(h, w)] * B if sizes is None else (sizes.cpu() if torch.is_tensor(sizes) else sizes), dtype=np.int32).reshape(-1, 2)
+    if sz.shape[0] != B or (sz < 1).any():
+        raise L.MCAVError("%s: sizes must be %d positive (H, W) pairs, got %r" % (what, B, sz.tolist()))
+    return sz
+
+
+def _matrices(M, B, shape, what):
+    try:
+        return np.broadcast_to(np.asarray(M.cpu() if torch.is_tensor(M) else M, dtype=np.float64), (B,) + shape)
+    except ValueError:
+        raise L.MCAVError("%s must be %s or [B, %d, %d]" % (what, list(shape), shape[0], shape[1]))
+
+
+class GroundScale:
+    """The estimator's result, on the device: `rows` [B, 4] float32 = (scale, median height, ground pixels, status) per image, `scales` =
+    rows[:, 0] (a view; the fallback where status is 0), `mask` uint8 [B, h, w] with keep_mask.  Nothing is read back."""
+
+    def __init__(self, batch, device, mask_shape=None):
+        self.rows = torch.empty((int(batch), 4), dtype=torch.float32, device=device)
+        self.mask = None if mask_shape is None else torch.empty(mask_shape, dtype=torch.uint8, device=device)
+        self._meta_bytes, self._meta, self._ws = None, None, None
+
+    @property
+    def scales(self):
+        return self.rows[:, 0]
+
+
+def ground_scale(m, sizes=None, P=None, camera_height=1.65, max_angle_deg=5.0, box=None, min_ground=100, fallback=float("nan"),
+                 input="disparity", keep_mask=False, out=None):
+    """The metric scale of every image of a batch from its ground plane (mcav_ground_scale).
+    m: [B, h, w] or [B, 1, h, w] float32 on the GPU -- the network's sigmoid disparity, or depths with input="depth"; sizes: B pairs
+    (Hb, Wb), the resolution P describes (default (h, w)); P: [3, 4] or [B, 3, 4] (P_rect_02).  camera_height: the camera above the road in
+    metres (1.65 on KITTI); max_angle_deg: the cone around the camera's y axis a ground normal lies in; box: (y0, y1, x0, x1) in network
+    pixels (or B of them) to look in, None = everywhere; an image with fewer than min_ground ground pixels gets `fallback` and status 0.
+    out: a GroundScale to reuse (needed under graph capture).  -> GroundScale; no host synchronisation."""
+    m = _plane(m, "ground_scale")
+    B, h, w = m.shape
+    if P is None:
+        raise L.MCAVError("ground_scale: P (the camera's 3x4 projection) is required")
+    if input not in ("disparity", "depth"):
+        raise L.MCAVError("ground_scale: input must be 'disparity' or 'depth', got %r" % (input,))
+    sz = _sizes(sizes, B, h, w, "ground_scale")
+    Pm = _matrices(P, B, (3, 4), "ground_scale: P")
+    calib = np.zeros((B, 28), np.float64)
+    calib[:, :12] = Pm.reshape(B, 12)
+    parts = [calib.reshape(-1).view(np.uint8), np.ascontiguousarray(sz).reshape(-1).view(np.uint8)]
+    if box is not None:
+        bx = np.asarray(box, dtype=np.int32)
+        try:
+            bx = np.ascontiguousarray(np.broadcast_to(bx, (B, 4)))
+        except ValueError:
+            raise L.MCAVError("ground_scale: box must be (y0, y1, x0, x1) or %d of them, got %r" % (B, box))
+        parts.append(bx.reshape(-1).view(np.uint8))
+    meta = np.concatenate(parts).tobytes()
+    dev = m.device
+    if out is None:
+        out = GroundScale(B, dev, (B, h, w) if keep_mask else None)
+    elif not isinstance(out, GroundScale) or out.rows.shape[0] != B or out.rows.device != dev:
+        raise L.MCAVError("ground_scale: out must be a GroundScale of %d images on %s" % (B, dev))
+    if keep_mask and (out.mask is None or tuple(out.mask.shape) != (B, h, w)):
+        raise L.MCAVError("ground_scale: out holds no [%d, %d, %d] mask" % (B, h, w))
+    hl = L.lib()
+    nbytes = hl.mcav_ground_scale_workspace_bytes(B, h, w)
+    if nbytes == 0:
+        raise L.MCAVError("ground_scale: a batch of %d x %d x %d pixels is refused (h, w >= 3, fewer than 2^31 pixels)" % (B, h, w))
+    if out._meta_bytes != meta:                 # as project_batch: a second call with the same calibration copies nothing
+        out._meta = torch.frombuffer(bytearray(meta), dtype=torch.uint8).pin_memory().to(dev, non_blocking=True)
+        out._meta_bytes = meta
+    if out._ws is None or out._ws.numel() < nbytes:
+        out._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    base = out._meta.data_ptr()
+    cos_max = float(np.float32(np.cos(np.deg2rad(np.float64(max_angle_deg)))))
+    with torch.cuda.device(dev):
+        L.check(hl.mcav_ground_scale(L.ptr(m), B, h, w, L.c_p(base + 224 * B), L.c_p(base), L.c_p(base + 232 * B if box is not None else 0),
+                                     float(camera_height), cos_max, int(min_ground), float(fallback),
+                                     GS_INPUT_DEPTH if input == "depth" else 0, L.ptr(out.rows), L.ptr(out.mask if keep_mask else None),
+                                     L.ptr(out._ws), out._ws.numel(), L.stream()), "mcav_ground_scale")
+    return out
 
 
 class PseudoLiDAR:
@@ -152,21 +256,24 @@ class PseudoLiDAR:
         step = int(self.sparsity) if self.sparsity else 1
         return cloud[:(valid + step - 1) // step]
 
+    def ground_scale(self, m, sizes=None, P=None, **kw):
+        """pseudo_lidar.ground_scale with the instance's P (unless one is given)"""
+        return ground_scale(m, sizes=sizes, P=self.P if P is None else P, **kw)
+
     def project_batch(self, m, sizes=None, P=None, T=None, input="disparity", scale=1.0, intensity=None, max_height=1.0, max_depth=None,
-                      beams=None, out=None, padded=None):
+                      beams=None, out=None, padded=None, ground=None):
         """m: [B, h, w] or [B, 1, h, w] float32 on the GPU -- the network's sigmoid disparity, or depths with input="depth".
         sizes: B pairs (Hb, Wb), the resolution P describes (default: (h, w)); padded: (Hg, Wg) bounding them (default: the largest).
-        P [3, 4] / [B, 3, 4], T [4, 4] / [B, 4, 4]: default the instance's.  scale multiplies the depth (pred_depth_scale_factor).
+        P [3, 4] / [B, 3, 4], T [4, 4] / [B, 4, 4]: default the instance's.  scale multiplies the depth (pred_depth_scale_factor): a
+        number for the whole batch, a float32 tensor [B] on the GPU with one per image (an image whose scale is not finite and positive
+        gets an empty cloud), or "ground": ground_scale's estimate with this batch's sizes and P and the keywords in the dict `ground`,
+        handed on on the device (the GroundScale is kept as out.ground; `ground` may hold camera_height, max_angle_deg, box, min_ground,
+        fallback and keep_mask).  A scale tensor that is not contiguous (a column of a GroundScale's rows) is packed into a new tensor on
+        every call: under graph capture hand over a contiguous one.
         intensity: a plane shaped as m for the 4th column (default 0).  max_height: the reference's max_high cut; max_depth: None = off.
         beams: a beam_tables result = one return per cell instead of the dense cloud; self.sparsity applies to the dense cloud only.
         out: a CloudBatch to reuse (needed under graph capture).  -> CloudBatch; no host synchronisation."""
-        if not torch.is_tensor(m):
-            raise L.MCAVError("project_batch: m must be a tensor on the GPU")
-        if m.dim() == 4 and m.shape[1] == 1:
-            m = m[:, 0]
-        if m.dim() != 3:
-            raise L.MCAVError("project_batch: m must be [B, h, w] or [B, 1, h, w], got %s" % (tuple(m.shape),))
-        m = L.dev(m.contiguous() if m.is_cuda else m, "m")
+        m = _plane(m, "project_batch")
         B, h, w = m.shape
         if input not in ("disparity", "depth"):
             raise L.MCAVError("project_batch: input must be 'disparity' or 'depth', got %r" % (input,))
@@ -176,9 +283,7 @@ class PseudoLiDAR:
             if tuple(intensity.shape) != (B, h, w):
                 raise L.MCAVError("project_batch: intensity must be shaped as m, got %s" % (tuple(intensity.shape),))
             intensity = L.dev(intensity.contiguous() if intensity.is_cuda else intensity, "intensity")
-        sz = np.asarray([(h, w)] * B if sizes is None else (sizes.cpu() if torch.is_tensor(sizes) else sizes), dtype=np.int32).reshape(-1, 2)
-        if sz.shape[0] != B or (sz < 1).any():
-            raise L.MCAVError("project_batch: sizes must be %d positive (H, W) pairs, got %r" % (B, sz.tolist()))
+        sz = _sizes(sizes, B, h, w, "project_batch")
         Hg, Wg = (int(sz[:, 0].max()), int(sz[:, 1].max())) if padded is None else (int(padded[0]), int(padded[1]))
         if (sz[:, 0] > Hg).any() or (sz[:, 1] > Wg).any():
             raise L.MCAVError("project_batch: sizes %r exceed the padded size (%d, %d)" % (sz.tolist(), Hg, Wg))
@@ -217,10 +322,36 @@ class PseudoLiDAR:
             out._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         ws, meta = out._ws, out._meta
         elev, azim = beams.on(dev) if beams is not None else (None, None)
+        scales = None
+        if isinstance(scale, str):
+            if scale != "ground":
+                raise L.MCAVError("project_batch: scale must be a number, a tensor [B] or 'ground', got %r" % (scale,))
+            gkw = dict(ground or {})
+            unknown = set(gkw) - {"camera_height", "max_angle_deg", "box", "min_ground", "fallback", "keep_mask"}
+            if unknown:
+                raise L.MCAVError("project_batch: ground= takes camera_height, max_angle_deg, box, min_ground, fallback and keep_mask, "
+                                  "not %s (sizes, P and input are the batch's)" % sorted(unknown))
+            if out.ground is not None and gkw.get("keep_mask") and out.ground.mask is None:
+                out.ground = None                                                      # made without a mask by an earlier call: a new one
+            out.ground = ground_scale(m, sizes=sz, P=Pm, input=input, out=out.ground, **gkw)
+            if out._packed is None:
+                out._packed = torch.empty(B, dtype=torch.float32, device=dev)
+            scales, scale = out._packed.copy_(out.ground.scales), 1.0                  # column 0 of the rows, packed: B floats, same stream
+        elif torch.is_tensor(scale):
+            if tuple(scale.shape) != (B,):
+                raise L.MCAVError("project_batch: a scale tensor must be [%d], got %s" % (B, tuple(scale.shape)))
+            scales, scale = L.dev(scale.contiguous() if scale.is_cuda else scale, "scale"), 1.0
+        elif ground is not None:
+            raise L.MCAVError("project_batch: ground= has no meaning without scale='ground'")
         with torch.cuda.device(dev):
-            L.check(hl.mcav_pl_batch_project(L.ptr(m), B, h, w, Hg, Wg, L.c_p(meta.data_ptr() + 224 * B), L.c_p(meta.data_ptr()),
-                                             L.ptr(intensity), L.ptr(elev), L.ptr(azim), nb, na, float(scale), float(max_height),
-                                             float("inf") if max_depth is None else float(max_depth), sparsity,
-                                             PLB_INPUT_DEPTH if input == "depth" else 0, L.ptr(out.points), out.points.shape[0],
-                                             L.ptr(out.offsets), L.ptr(ws), ws.numel(), L.stream()), "mcav_pl_batch_project")
+            head = (L.ptr(m), B, h, w, Hg, Wg, L.c_p(meta.data_ptr() + 224 * B), L.c_p(meta.data_ptr()), L.ptr(intensity), L.ptr(elev),
+                    L.ptr(azim), nb, na, float(scale))
+            tail = (float(max_height), float("inf") if max_depth is None else float(max_depth), sparsity,
+                    PLB_INPUT_DEPTH if input == "depth" else 0, L.ptr(out.points), out.points.shape[0], L.ptr(out.offsets), L.ptr(ws),
+                    ws.numel(), L.stream())
+            if scales is None:
+                L.check(hl.mcav_pl_batch_project(*head, *tail), "mcav_pl_batch_project")
+            else:
+                out._scales = scales                                                   # alive as long as the cloud is
+                L.check(hl.mcav_pl_batch_project_scaled(*head, L.ptr(scales), *tail), "mcav_pl_batch_project_scaled")
         return out

@@ -1,1 +1,1 @@
-from .PseudoLiDAR import BeamTables, CloudBatch, PseudoLiDAR, beam_tables  # noqa: F401
+from .PseudoLiDAR import BeamTables, CloudBatch, GroundScale, PseudoLiDAR, beam_tables, ground_scale  # noqa: F401

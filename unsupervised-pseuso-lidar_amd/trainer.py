@@ -105,6 +105,8 @@ class Trainer:
             from dataloaders import UnSupKittiDataset
             dataset = UnSupKittiDataset(config, transforms=None)
         self.dataset = dataset
+        if self.validation is not None and self.validation['scaling'] == 'ground' and not getattr(dataset, "calibration", False):
+            raise ValueError("config validation.scaling: ground reads every frame's P_rect_02; set datasets.calibration: true")
         if self.augmentation is not None and not getattr(dataset, "raw", False):
             raise ValueError("config datasets.augmentation: color_jitter / flip run on the GPU loader's decoded bytes; this dataset gives "
                              "finished tensors")
@@ -299,12 +301,15 @@ class Trainer:
         loss = self.criterion.forward(tgt, ref_imgs, disps, poses, intrinsics, gt, **st)
         return [disps, poses], loss
 
-    VALIDATION_DEFAULTS = {'protocol': 'eigen', 'crop': 'garg', 'min_depth': 1e-3, 'max_depth': 80.0, 'median_scaling': True, 'scale': 1.0}
+    VALIDATION_DEFAULTS = {'protocol': 'eigen', 'crop': 'garg', 'min_depth': 1e-3, 'max_depth': 80.0, 'median_scaling': True, 'scale': 1.0,
+                           'scaling': None, 'camera_height': 1.65}
 
     @classmethod
     def validation_config(cls, cfg):
         """The top-level config key `validation` (None: validate() keeps the reference's per-batch compute_errors).  Its keys and defaults:
-        protocol: eigen, crop: garg (or eigen, or null = whole image), min_depth: 1e-3, max_depth: 80, median_scaling: true, scale: 1.0."""
+        protocol: eigen, crop: garg (or eigen, or null = whole image), min_depth: 1e-3, max_depth: 80, median_scaling: true, scale: 1.0,
+        scaling: median | ground | none (median and none are median_scaling true and false; ground scores the prediction at the metric scale
+        pseudo_lidar.ground_scale estimates from it, without median scaling, and needs datasets.calibration: true), camera_height: 1.65."""
         if cfg is None:
             return None
         unknown = set(cfg) - set(cls.VALIDATION_DEFAULTS)
@@ -317,6 +322,17 @@ class Trainer:
             raise ValueError("config validation.crop must be garg, eigen or null, got %r" % (v['crop'],))
         v['min_depth'], v['max_depth'], v['scale'] = float(v['min_depth']), float(v['max_depth']), float(v['scale'])
         v['median_scaling'] = bool(v['median_scaling'])
+        if v['scaling'] is None:
+            v['scaling'] = 'median' if v['median_scaling'] else 'none'
+        if v['scaling'] not in ('median', 'ground', 'none'):
+            raise ValueError("config validation.scaling must be median, ground or none, got %r" % (v['scaling'],))
+        if 'median_scaling' in cfg and cfg.get('scaling') is not None and v['median_scaling'] != (v['scaling'] == 'median'):
+            raise ValueError("config validation: scaling: %s contradicts median_scaling: %s; give one of the two keys"
+                             % (v['scaling'], str(v['median_scaling']).lower()))
+        v['median_scaling'] = v['scaling'] == 'median'
+        v['camera_height'] = float(v['camera_height'])
+        if not v['camera_height'] > 0:
+            raise ValueError("config validation.camera_height must be positive, got %r" % (v['camera_height'],))
         return v
 
     @torch.no_grad()
@@ -326,7 +342,7 @@ class Trainer:
         from evaluate import eval_depth_rows, reduce_rows
         v = self.validation
         self.depth_model.eval()
-        rows = []
+        rows, ground = [], []
         try:
             for samples in self.validation_loader:
                 if 'groundtruth_size' not in samples:
@@ -334,11 +350,18 @@ class Trainer:
                                      "a KITTI split); this loader gives ground truth resized to the network's input")
                 tgt = samples['tgt'].to(self.device, non_blocking=True)
                 gt = samples['groundtruth'].to(self.device, non_blocking=True)
-                rows.append(eval_depth_rows(gt, self.depth_model(tgt), samples['groundtruth_size'], v['crop'], v['min_depth'], v['max_depth'],
-                                            v['median_scaling'], v['scale']))
+                pred, scales = self.depth_model(tgt), None
+                if v['scaling'] == 'ground':
+                    from pseudo_lidar import ground_scale
+                    disp = pred[0] if isinstance(pred, (list, tuple)) else pred
+                    ground.append(ground_scale(disp.detach().to(torch.float32), sizes=samples['native_size'], P=samples['P_rect'],
+                                               camera_height=v['camera_height']).rows)
+                    scales = ground[-1][:, 0]
+                rows.append(eval_depth_rows(gt, pred, samples['groundtruth_size'], v['crop'], v['min_depth'], v['max_depth'],
+                                            v['median_scaling'], v['scale'], scales))
         finally:
             self.set_train()
-        return reduce_rows(rows)
+        return reduce_rows(rows, ground if v['scaling'] == 'ground' else None)
 
     @torch.no_grad()
     def validate(self):
