@@ -400,6 +400,39 @@ int mcav_ground_scale(const float* m, int B, int h, int w, const int* sizes, con
                       float cos_max, int min_ground, float fallback, int flags, float* rows, unsigned char* mask_out, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* Cloud batch -> pillars, the input of a LiDAR 3-D detector (PointPillars / SECOND / OpenPCDet: voxels [P, N, C], coords [P, 4],
+ * num_points [P]).  The definition is tests/pillar_ref.py; the arithmetic is csrc/pillar_math.h.
+ *   input    points [n_max, 4] float32 (x, y, z, i) and offsets int32 [B + 1] (offsets[0] = 0, ascending) on the device, as
+ *            mcav_pl_batch_project leaves them: image b owns rows offsets[b] .. offsets[b + 1]; n = min(offsets[B], n_max) and rows at and
+ *            beyond n are never read.  The host does not know n: launches are sized by n_max.
+ *   grid     nx x ny cells of vx x vy from (x0, y0), one cell in z: [z0, z1)
+ *   cell     float32, every operation rounded on its own: fx = floorf((x - x0) / vx) (IEEE division), fy likewise; the point is kept iff
+ *            0 <= fx < nx, 0 <= fy < ny and z0 <= z < z1, compared as floats and converted to int only then: a NaN or an infinite
+ *            coordinate drops the point, -0.0 is 0.  Cell = (b, iy, ix).
+ *   pillars  the non-empty cells in ascending (b, iy, ix) order; pillar_offsets int32 [B + 1]: image b owns pillars
+ *            pillar_offsets[b] .. pillar_offsets[b + 1], exact whatever the capacity; rows at and beyond capacity are not written.
+ *   slots    the points of the cell with the min(count, max_points) smallest row indices, in ascending index order (second.pytorch's
+ *            "first N in cloud order"); num_points = min(count, max_points); the slots behind them are +0.0 in every column.
+ *   coords   (b, 0, iy, ix): OpenPCDet's (batch, z, y, x)
+ *   columns  C = 4: x, y, z, i, copied bit for bit.  MCAV_PILLAR_DECORATE: C = 9; columns 4..6 = x - mx, y - my, z - mz with m the float64
+ *            sum over the kept slots in slot order, divided by num_points in float64 and rounded once to float32; columns 7..8 =
+ *            x - ((float)ix * vx + (vx * 0.5f + x0)) and the same in y, every product and sum rounded on its own.
+ * voxels: device [capacity, max_points, C] float32; coords: device [capacity, 4] int32; num_points: device [capacity] int32.
+ * Integer atomics only, and no output depends on the order in which they land: two runs give the same bytes.  No host synchronisation,
+ * allocation or copy (one hipMemsetAsync of the cell counters): the call can be captured.  6 launches.
+ * Workspace (mcav_pillarize_workspace_bytes, 0 for sizes that are refused; scratch of one call, no zero-fill, each piece rounded up to 256
+ * bytes): 4 (B ny nx + 1) + 8 ceil(B ny nx / 1024) + 12 n_max + 4 min(n_max, B ny nx) bytes.
+ * Returns MCAV_E_INVALID for a null pointer, B <= 0, B > 65535, n_max < 0, n_max >= 2^31, B * ny * nx >= 2^31, nx or ny < 1, max_points
+ * outside [1, 64], capacity < 0, a vx or vy that is not finite and positive, a non-finite x0 or y0, z1 <= z0 (a NaN included), unknown flag
+ * bits, a points, coords or workspace address that is no multiple of 16, or a voxels address that is no multiple of 16 when
+ * max_points * C is a multiple of 4 (the row blocks then go out in 16-byte stores; of 4 otherwise); MCAV_E_WORKSPACE for a short
+ * workspace; nothing is launched then. */
+#define MCAV_PILLAR_DECORATE 1
+size_t mcav_pillarize_workspace_bytes(int B, long long n_max, int ny, int nx);
+int mcav_pillarize(const float* points, const int* offsets, int B, long long n_max, float x0, float y0, float z0, float z1, float vx,
+                   float vy, int nx, int ny, int max_points, int flags, float* voxels, int* coords, int* num_points, long long capacity,
+                   int* pillar_offsets, void* workspace, size_t workspace_bytes, void* stream);
+
 /* KITTI Eigen ground truth from raw Velodyne scans (monodepth2 kitti_utils.generate_depth_map), the forward direction of the projection
  * above: scan -> sparse depth map, per image of a batch.  The definition is tests/velo_ref.py; for image b with points p = (x, y, z, r)
  * (float32, as stored in the .bin file; r is never read), P = P[b] (3x4 velodyne -> image, float64) and true size (Hb, Wb) = sizes[b]:

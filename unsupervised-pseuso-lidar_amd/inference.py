@@ -3,10 +3,15 @@
     inf = Inference(config, checkpoint="pretrained/model.pth")
     disp = inf.disparity(images)                       # [B, 1, h, w], evaluation mode, no gradients
     cb = inf.clouds(samples, beams=beam_tables())      # a pseudo_lidar.CloudBatch for one loader batch
+    pb = inf.pillars(samples, max_points=32)           # a pseudo_lidar.PillarBatch: what a LiDAR 3-D detector reads
     n = inf.export("out")                              # out/<date>/<drive>/pseudo_velodyne/data/<frame>.bin for every frame of the split
 
     python inference.py --config C --checkpoint X --out DIR [--beams NB NA] [--scale S | --scale ground] [--max-depth D]
                         [--camera-height M] [--ground-angle DEG] [--ground-min N]
+                        [--pillars [--pillar-size VX VY] [--pillar-points N] [--pillar-range X0 X1 Y0 Y1 Z0 Z1]]
+
+--pillars also writes out/<date>/<drive>/pseudo_pillars/data/<frame>.npz (voxels [P, N, 4], coords [P, 4] = (image in its batch, 0, iy,
+ix), num_points [P]) beside every .bin: the cloud voxelised on the GPU (pseudo_lidar.pillarize; default PointPillars' KITTI grid).
 
 --scale ground gives every frame its own metric scale from its ground plane (pseudo_lidar.ground_scale: no ground truth, no stereo); a
 frame without enough ground pixels gets an empty cloud.
@@ -23,7 +28,7 @@ import numpy as np
 import torch
 import yaml
 
-from pseudo_lidar import PseudoLiDAR, beam_tables
+from pseudo_lidar import PillarGrid, PseudoLiDAR, beam_tables
 
 
 class Inference:
@@ -72,6 +77,15 @@ class Inference:
         return self.projector.project_batch(self.disparity(samples['tgt']), sizes=samples['native_size'], P=samples['P_rect'],
                                             T=samples['T_velo_cam'], **kw)
 
+    @torch.no_grad()
+    def pillars(self, samples, grid=None, max_points=32, decorate=False, **cloud_kw):
+        """One batch of a datasets.calibration loader -> PillarBatch: clouds(samples, **cloud_kw), voxelised on the device
+        (pseudo_lidar.pillarize).  The CloudBatch stays reachable as `.cloud`."""
+        cloud = self.clouds(samples, **cloud_kw)
+        pb = cloud.pillars(grid=grid, max_points=max_points, decorate=decorate)
+        pb.cloud = cloud
+        return pb
+
     def loader(self):
         """Every frame of the split, in order, with its calibration"""
         from dataloaders import PrefetchLoader, UnSupKittiDataset, raw_collate
@@ -87,21 +101,38 @@ class Inference:
                               native_groundtruth=bool(getattr(self.dataset, "native_gt", False)))
 
     @staticmethod
-    def cloud_path(out_dir, image_path):
-        """<out_dir>/<date>/<drive>/pseudo_velodyne/data/<frame>.bin of .../<date>/<drive>/image_02/data/<frame>.png"""
+    def _frame_path(out_dir, image_path, folder, ext):
         parts = os.path.normpath(image_path).split(os.sep)
         if len(parts) < 5 or parts[-2] != "data":
             raise ValueError("Inference.export: %r is not a KITTI raw frame (<date>/<drive>/image_02/data/<frame>.png)" % image_path)
-        return os.path.join(out_dir, parts[-5], parts[-4], "pseudo_velodyne", "data", os.path.splitext(parts[-1])[0] + ".bin")
+        return os.path.join(out_dir, parts[-5], parts[-4], folder, "data", os.path.splitext(parts[-1])[0] + ext)
 
-    def export(self, out_dir, loader=None, **kw):
-        """Writes one KITTI .bin (float32 x y z i) per frame of the split and returns the number of files."""
+    @staticmethod
+    def cloud_path(out_dir, image_path):
+        """<out_dir>/<date>/<drive>/pseudo_velodyne/data/<frame>.bin of .../<date>/<drive>/image_02/data/<frame>.png"""
+        return Inference._frame_path(out_dir, image_path, "pseudo_velodyne", ".bin")
+
+    @staticmethod
+    def pillar_path(out_dir, image_path):
+        """<out_dir>/<date>/<drive>/pseudo_pillars/data/<frame>.npz of .../<date>/<drive>/image_02/data/<frame>.png"""
+        return Inference._frame_path(out_dir, image_path, "pseudo_pillars", ".npz")
+
+    def export(self, out_dir, loader=None, pillars=None, **kw):
+        """Writes one KITTI .bin (float32 x y z i) per frame of the split and returns the number of frames.  pillars: None, or a dict of
+        pillarize's keywords (grid, max_points, decorate; {} for the defaults): every frame's .npz of voxels, coords and num_points is
+        written too, at the cost of one more read-back of offsets and one of the used rows per batch."""
         n = 0
         for samples in (self.loader() if loader is None else loader):
             paths = [self.cloud_path(out_dir, p) for p in samples['path']]
             for p in paths:
                 os.makedirs(os.path.dirname(p), exist_ok=True)
-            self.clouds(samples, **kw).save_bin(paths)
+            cloud = self.clouds(samples, **kw)
+            cloud.save_bin(paths)
+            if pillars is not None:
+                npz = [self.pillar_path(out_dir, p) for p in samples['path']]
+                for p in npz:
+                    os.makedirs(os.path.dirname(p), exist_ok=True)
+                cloud.pillars(**pillars).save_npz(npz)
             n += len(paths)
         return n
 
@@ -111,7 +142,15 @@ def scale_argument(text):
     return "ground" if text.strip().lower() == "ground" else float(text)
 
 
-def main(argv=None):
+def pillar_arguments(args):
+    """--pillars and its options -> export's `pillars` (None without the flag); a bad grid is refused before anything is loaded"""
+    if not args.pillars:
+        return None
+    r = args.pillar_range
+    return dict(grid=PillarGrid(x=(r[0], r[1]), y=(r[2], r[3]), z=(r[4], r[5]), size=tuple(args.pillar_size)), max_points=args.pillar_points)
+
+
+def build_parser():
     ap = argparse.ArgumentParser(description="checkpoint + KITTI split -> pseudo-LiDAR .bin clouds")
     ap.add_argument("--config", required=True)
     ap.add_argument("--checkpoint", required=True)
@@ -123,7 +162,17 @@ def main(argv=None):
     ap.add_argument("--camera-height", type=float, default=1.65, help="--scale ground: the camera above the road in metres")
     ap.add_argument("--ground-angle", type=float, default=5.0, help="--scale ground: the cone around 'down' a ground normal lies in, degrees")
     ap.add_argument("--ground-min", type=int, default=100, help="--scale ground: fewer ground pixels than this and the frame gets no cloud")
-    args = ap.parse_args(argv)
+    ap.add_argument("--pillars", action="store_true", help="also write <date>/<drive>/pseudo_pillars/data/<frame>.npz: the cloud voxelised")
+    ap.add_argument("--pillar-size", nargs=2, type=float, default=(0.16, 0.16), metavar=("VX", "VY"), help="--pillars: a pillar in metres")
+    ap.add_argument("--pillar-points", type=int, default=32, help="--pillars: the points kept per pillar (1..64), the first in cloud order")
+    ap.add_argument("--pillar-range", nargs=6, type=float, default=(0.0, 69.12, -39.68, 39.68, -3.0, 1.0),
+                    metavar=("X0", "X1", "Y0", "Y1", "Z0", "Z1"), help="--pillars: the grid's extent in the velodyne frame, metres")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    pillars = pillar_arguments(args)
     with open(args.config) as f:
         config = yaml.full_load(f)
     kw = dict(scale=args.scale, max_depth=args.max_depth)
@@ -131,8 +180,8 @@ def main(argv=None):
         kw["ground"] = dict(camera_height=args.camera_height, max_angle_deg=args.ground_angle, min_ground=args.ground_min)
     if args.beams:
         kw["beams"] = beam_tables(args.beams[0], args.beams[1])
-    n = Inference(config, args.checkpoint).export(args.out, **kw)
-    print("wrote %d clouds under %s" % (n, args.out))
+    n = Inference(config, args.checkpoint).export(args.out, pillars=pillars, **kw)
+    print("wrote %d clouds%s under %s" % (n, " and their pillars" if pillars is not None else "", args.out))
 
 
 if __name__ == "__main__":

@@ -15,6 +15,10 @@ inside, per-image calibration, and either the dense cloud or one return per (bea
 camera_height / median height of the pixels whose surface normal points down (mcav_ground_scale; the definition is
 tests/ground_scale_ref.py).  `project_batch(..., scale="ground")` runs it and hands the per-image scales on, on the device;
 `project_batch(..., scale=<tensor [B]>)` takes any per-image scales.
+
+`pillarize(points, offsets)` / `CloudBatch.pillars()` turn a cloud batch into what a LiDAR 3-D detector reads (PointPillars / SECOND /
+OpenPCDet): a `PillarBatch` of voxels [P, N, C], coords [P, 4] = (batch, z, y, x) and num_points [P] on a `PillarGrid`, the first N points
+of every non-empty cell in cloud order (mcav_pillarize; the definition is tests/pillar_ref.py).  Still nothing is read back.
 """
 import ctypes
 
@@ -35,10 +39,14 @@ L.register({
     "mcav_ground_scale_workspace_bytes": (L.c_sz, [L.c_i] * 3),
     "mcav_ground_scale": (L.c_i, [L.c_p, L.c_i, L.c_i, L.c_i, L.c_p, L.c_p, L.c_p, L.c_f, L.c_f, L.c_i, L.c_f, L.c_i, L.c_p, L.c_p, L.c_p,
                                   L.c_sz, L.c_p]),
+    "mcav_pillarize_workspace_bytes": (L.c_sz, [L.c_i, ctypes.c_longlong, L.c_i, L.c_i]),
+    "mcav_pillarize": (L.c_i, [L.c_p, L.c_p, L.c_i, ctypes.c_longlong] + [L.c_f] * 6 + [L.c_i] * 4 + [L.c_p] * 3 + [ctypes.c_longlong, L.c_p,
+                               L.c_p, L.c_sz, L.c_p]),
 })
 
 PLB_INPUT_DEPTH = 1                            # include/mcav_depth.h MCAV_PLB_INPUT_DEPTH
 GS_INPUT_DEPTH = 1                             # include/mcav_depth.h MCAV_GS_INPUT_DEPTH
+PILLAR_DECORATE = 1                            # include/mcav_depth.h MCAV_PILLAR_DECORATE
 
 
 class BeamTables:
@@ -111,6 +119,148 @@ class CloudBatch:
         host = self.points[:int(o[-1])].cpu().numpy()
         for b, path in enumerate(paths):
             host[int(o[b]):int(o[b + 1])].tofile(path)
+
+    def pillars(self, **kw):
+        """pillarize(self.points, self.offsets, **kw) -> PillarBatch (grid, max_points, capacity, decorate, out)"""
+        return pillarize(self.points, self.offsets, **kw)
+
+
+class PillarGrid:
+    """The cells of pillarize: ranges x, y, z in metres (velodyne frame) and the pillar's size (vx, vy); one cell in z.  nx =
+    round((x1 - x0) / vx), ny likewise.  The default is PointPillars' KITTI grid: 432 x 496 pillars of 0.16 m.  Empty, reversed or
+    non-finite ranges and sizes are refused.  The kernels take the scalars as float32."""
+
+    def __init__(self, x=(0.0, 69.12), y=(-39.68, 39.68), z=(-3.0, 1.0), size=(0.16, 0.16)):
+        try:
+            vals = [float(v) for pair in (x, y, z, size) for v in pair]
+            if len(vals) != 8 or any(len(pair) != 2 for pair in (x, y, z, size)):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise L.MCAVError("PillarGrid: x, y, z are (low, high) pairs and size is (vx, vy), got %r %r %r %r" % (x, y, z, size))
+        with np.errstate(over="ignore"):
+            f32 = np.array(vals, np.float64).astype(np.float32)
+        if not np.isfinite(f32).all():
+            raise L.MCAVError("PillarGrid: every range and size must be finite (in float32), got %r" % (vals,))
+        self.x, self.y, self.z, self.size = tuple(vals[0:2]), tuple(vals[2:4]), tuple(vals[4:6]), tuple(vals[6:8])
+        if not (f32[6] > 0 and f32[7] > 0):
+            raise L.MCAVError("PillarGrid: the pillar size must be positive, got %r" % (self.size,))
+        if not (f32[1] > f32[0] and f32[3] > f32[2] and f32[5] > f32[4]):
+            raise L.MCAVError("PillarGrid: empty range in x %r, y %r or z %r" % (self.x, self.y, self.z))
+        self.nx = int(round((self.x[1] - self.x[0]) / self.size[0]))
+        self.ny = int(round((self.y[1] - self.y[0]) / self.size[1]))
+        if self.nx < 1 or self.ny < 1 or self.nx * self.ny >= 2 ** 31:
+            raise L.MCAVError("PillarGrid: %d x %d cells" % (self.nx, self.ny))
+
+    def scalars(self):
+        """x0, y0, z0, z1, vx, vy as the C call takes them"""
+        return self.x[0], self.y[0], self.z[0], self.z[1], self.size[0], self.size[1]
+
+    def __repr__(self):
+        return "PillarGrid(x=%r, y=%r, z=%r, size=%r) [%d x %d]" % (self.x, self.y, self.z, self.size, self.nx, self.ny)
+
+
+class PillarBatch:
+    """The pillars of a batch on the device: `voxels` [capacity, N, C] float32, `coords` [capacity, 4] int32 = (image, 0, iy, ix),
+    `num_points` [capacity] int32 and `offsets` int32 [B + 1]; image b owns rows offsets[b]:offsets[b+1].  Rows beyond the capacity were
+    not written (offsets stay exact).  Nothing is read back until asked."""
+
+    def __init__(self, batch, capacity, max_points, columns, device):
+        self.voxels = torch.empty((int(capacity), int(max_points), int(columns)), dtype=torch.float32, device=device)
+        self.coords = torch.empty((int(capacity), 4), dtype=torch.int32, device=device)
+        self.num_points = torch.empty(int(capacity), dtype=torch.int32, device=device)
+        self.offsets = torch.zeros(int(batch) + 1, dtype=torch.int32, device=device)
+        self.grid = None
+        self._host, self._ws = None, None
+
+    def __len__(self):
+        return self.offsets.numel() - 1
+
+    def counts(self):
+        """offsets on the host (numpy int64 [B + 1]): the one read-back of the batch, kept until the next call into this object."""
+        if self._host is None:
+            self._host = self.offsets.cpu().numpy().astype(np.int64)
+        return self._host
+
+    def split(self):
+        """-> B tuples (voxels, coords, num_points) of views, one per image (clipped to the capacity)"""
+        o = np.minimum(self.counts(), self.voxels.shape[0])
+        return [(self.voxels[int(o[b]):int(o[b + 1])], self.coords[int(o[b]):int(o[b + 1])], self.num_points[int(o[b]):int(o[b + 1])])
+                for b in range(len(self))]
+
+    def save_npz(self, paths):
+        """One device -> host copy of the used prefix (the three arrays packed on the device), then one .npz per image with `voxels`,
+        `coords` and `num_points`; coords keep the image's index within this batch in column 0."""
+        paths = list(paths)
+        if len(paths) != len(self):
+            raise L.MCAVError("save_npz: %d paths for %d images" % (len(paths), len(self)))
+        o = self.counts()
+        P = int(o[-1])
+        if P > self.voxels.shape[0]:
+            raise L.MCAVError("save_npz: the batch has %d pillars, the buffers hold %d" % (P, self.voxels.shape[0]))
+        N, C = self.voxels.shape[1:]
+        host = torch.cat([self.voxels[:P].reshape(-1).view(torch.int32), self.coords[:P].reshape(-1), self.num_points[:P]]).cpu().numpy()
+        vox = host[:P * N * C].view(np.float32).reshape(P, N, C)
+        coords = host[P * N * C:P * N * C + 4 * P].reshape(P, 4)
+        num = host[P * N * C + 4 * P:]
+        for b, path in enumerate(paths):
+            lo, hi = int(o[b]), int(o[b + 1])
+            with open(path, "wb") as f:
+                np.savez(f, voxels=vox[lo:hi], coords=coords[lo:hi], num_points=num[lo:hi])
+
+
+def pillarize(points, offsets, grid=None, max_points=32, capacity=None, decorate=False, out=None):
+    """A cloud batch -> pillars (mcav_pillarize).  points: [n_max, 4] float32 (x, y, z, i) and offsets: int32 [B + 1] on the GPU, as a
+    CloudBatch holds them (rows at and beyond offsets[B] are never read).  grid: a PillarGrid (default: PointPillars' KITTI grid).
+    max_points: N, the slots of a pillar, 1..64: the first N points of the cell in cloud order.  capacity: the rows of the output, default
+    min(n_max, B * ny * nx) -- every pillar there can be; with fewer, the pillars beyond are dropped and offsets stay exact.
+    decorate: C = 9 instead of 4: PointPillars' offsets from the pillar's mean (3) and from the cell's centre (2).
+    out: a PillarBatch to reuse with its workspace (needed under graph capture).  -> PillarBatch; no host synchronisation."""
+    if not torch.is_tensor(points) or not torch.is_tensor(offsets):
+        raise L.MCAVError("pillarize: points and offsets must be tensors on the GPU")
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise L.MCAVError("pillarize: points must be [n, 4] (x, y, z, i), got %s" % (tuple(points.shape),))
+    if offsets.dim() != 1 or offsets.numel() < 2:
+        raise L.MCAVError("pillarize: offsets must be [B + 1], got %s" % (tuple(offsets.shape),))
+    grid = PillarGrid() if grid is None else grid
+    if not isinstance(grid, PillarGrid):
+        raise L.MCAVError("pillarize: grid must be a PillarGrid, got %r" % (grid,))
+    N = int(max_points)
+    if not 1 <= N <= 64:
+        raise L.MCAVError("pillarize: max_points must be in 1..64, got %r" % (max_points,))
+    points, offsets = L.dev(points, "points"), L.dev(offsets, "offsets", torch.int32)
+    n_max, B = points.shape[0], offsets.numel() - 1
+    if n_max == 0:
+        raise L.MCAVError("pillarize: points holds no rows")
+    C = 9 if decorate else 4
+    cells = B * grid.ny * grid.nx
+    capacity = min(n_max, cells) if capacity is None else int(capacity)
+    if capacity < 1:
+        raise L.MCAVError("pillarize: capacity must be positive, got %d" % capacity)
+    dev = points.device
+    if out is None:
+        out = PillarBatch(B, capacity, N, C, dev)
+    elif (not isinstance(out, PillarBatch) or len(out) != B or out.voxels.device != dev or tuple(out.voxels.shape[1:]) != (N, C)):
+        raise L.MCAVError("pillarize: out must be a PillarBatch of %d images with [*, %d, %d] voxels on %s" % (B, N, C, dev))
+    else:
+        L.dev(out.voxels, "out.voxels")
+        for t, name, shape in ((out.coords, "out.coords", (out.voxels.shape[0], 4)), (out.num_points, "out.num_points", (out.voxels.shape[0],)),
+                               (out.offsets, "out.offsets", (B + 1,))):
+            if L.dev(t, name, torch.int32).device != dev or tuple(t.shape) != shape:
+                raise L.MCAVError("pillarize: %s must be %s on %s, got %s on %s" % (name, list(shape), dev, list(t.shape), t.device))
+        capacity = out.voxels.shape[0]
+    hl = L.lib()
+    nbytes = hl.mcav_pillarize_workspace_bytes(B, n_max, grid.ny, grid.nx)
+    if nbytes == 0:
+        raise L.MCAVError("pillarize: %d images of %d x %d cells with %d rows are refused (B <= 65535, fewer than 2^31 cells and rows)"
+                          % (B, grid.ny, grid.nx, n_max))
+    out._host, out.grid = None, grid
+    if out._ws is None or out._ws.numel() < nbytes:
+        out._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(hl.mcav_pillarize(L.ptr(points), L.ptr(offsets), B, n_max, *grid.scalars(), grid.nx, grid.ny, N,
+                                  PILLAR_DECORATE if decorate else 0, L.ptr(out.voxels), L.ptr(out.coords), L.ptr(out.num_points), capacity,
+                                  L.ptr(out.offsets), L.ptr(out._ws), out._ws.numel(), L.stream()), "mcav_pillarize")
+    return out
 
 
 def _plane(m, what):
