@@ -433,6 +433,54 @@ int mcav_pillarize(const float* points, const int* offsets, int B, long long n_m
                    float vy, int nx, int ny, int max_points, int flags, float* voxels, int* coords, int* num_points, long long capacity,
                    int* pillar_offsets, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Graph-based depth correction from sparse LiDAR (GDC): You et al., "Pseudo-LiDAR++: Accurate Depth for 3D Object Detection in Autonomous
+ * Driving", ICLR 2020, section 4; the reference's notes pseudo-lidar/PL_development/research/pseudo_lidar++.md: "create a KNN graph; use
+ * sparse LiDAR point clouds to bias and correct depth".  A predicted depth map has the right local shape and a smooth error; a few exact
+ * LiDAR depths are propagated over it while the local shape is kept.  The definition is tests/gdc_ref.py; the per-pixel arithmetic is
+ * csrc/gdc_math.h.  depth, sparse: device [B, H, W] float32 on one grid (sparse is 0 where there is no return); K: device [B, 4] float32
+ * = (fx, fy, cx, cy) of that grid.
+ *
+ * mcav_gdc_graph -- the windowed KNN graph and its locally-linear-embedding weights:
+ *   valid    min_depth < depth <= max_depth, compared as floats (NaN and +-inf drop out); known: valid and sparse in the same range
+ *   point    X = ((u - cx) / fx * z, (v - cy) / fy * z, z), float32, every quotient and product rounded on its own; positions come from
+ *            the PREDICTED depth for known pixels too (Pseudo-LiDAR++)
+ *   graph    the candidates of pixel i are the valid j != i of the (2 radius + 1)^2 window around it, clipped to the image, whose squared
+ *            distance ((dx dx + dy dy) + dz dz) is below +inf; its neighbours are the min(k, #candidates) nearest, ties to the lower
+ *            pixel index, stored in ascending (distance, index) order.  A window that covers the image gives exact KNN.
+ *   weights  sklearn.manifold.barycenter_weights on the scalar depths: d_j = z_j - z_i, C = d d^T + lam I, lam = reg |d|^2 (reg where
+ *            |d|^2 = 0), w = C^-1 1 / sum(C^-1 1), through Sherman-Morrison: w_j ~ 1 - d_j s / (lam + q), s = sum d_j, q = sum d_j^2 in
+ *            neighbour order
+ *   nbr      device int32 [B, H, W, k]: v * W + u of the neighbour, -1 in unused slots; weights: device float32 [B, H, W, k], +0.0 in
+ *            unused slots; flags: device uint8 [B, H, W]: bit 0 = in the graph (valid, with a candidate), bit 1 = known.
+ *   One launch; every element of nbr, weights and flags is written.
+ *
+ * mcav_gdc_solve -- with M = I - W over the graph pixels, L the known graph pixels and U the others: z'_L = sparse_L, z'_U minimises
+ * |M z'|^2.  Conjugate gradient on the normal equations from z'_U = depth_U: r = -(M^T M z')_U, p = r, rs = |r|^2, then per iteration
+ *   q = M p, alpha = rs / |q|^2, z'_U += alpha p, r -= alpha (M^T q)_U, rs' = |r|^2, beta = rs' / rs, p = r + beta p.
+ * Vectors and weights are float32; inner products are float64 (per-workgroup sums added in a fixed order by the image's last workgroup);
+ * (M v)_i sums in neighbour order, (M^T q)_j in ascending source order (a CSR built by scanning j's window: no atomics, no sort).  An
+ * image is done once rs <= tol^2 rs0, rs is not positive or |q|^2 is not positive; at most `iters` iterations; the workgroups of a
+ * finished image exit on its flag.
+ *   out      device [B, H, W] float32: z' on graph pixels (a known graph pixel holds its sparse value bit for bit), the bits of depth
+ *            elsewhere; an image with fewer than min_known known graph pixels is passed through unchanged
+ *   info     device [B, 4] float32: graph pixels, known graph pixels, iterations run, rs / rs0 (1 for a passed-through image, 0 where
+ *            rs0 is not positive)
+ * nbr entries outside [0, H W) are skipped, so no graph makes the call read out of bounds.  7 + 3 iters launches and one
+ * hipMemsetAsync of the call's counters and tickets; no host synchronisation, allocation or float atomics: the call can be captured,
+ * and two runs give the same bytes.
+ * Workspace (mcav_gdc_workspace_bytes, 0 for sizes that are refused; scratch of one call, shared by both entries; each piece rounded up
+ * to 256 bytes): (8 k + 12) B H W + 4 B G 256 + 12 B G + 12 B ceil(G / 16) + 44 B bytes with G = ceil(H W / 256).
+ * Both return MCAV_E_INVALID for a null pointer, B <= 0, B > 65535, H or W <= 0, H W > 2^24, k outside [1, 16], radius outside [1, 7],
+ * k B G 256 >= 2^31; mcav_gdc_graph also for a reg that is not positive and finite, min_depth < 0 or max_depth <= min_depth (a NaN
+ * included), more than 65535 tile rows; mcav_gdc_solve also for iters < 0, a tol that is negative or NaN, out == depth or sparse, a
+ * workspace address that is no multiple of 16; MCAV_E_WORKSPACE for a short workspace; nothing is launched then. */
+size_t mcav_gdc_workspace_bytes(int B, int H, int W, int k, int radius);
+int mcav_gdc_graph(const float* depth, const float* sparse, const float* K, int B, int H, int W, int k, int radius, float reg, float min_depth,
+                   float max_depth, int* nbr, float* weights, unsigned char* flags, void* workspace, size_t workspace_bytes, void* stream);
+int mcav_gdc_solve(const float* depth, const float* sparse, const int* nbr, const float* weights, const unsigned char* flags, int B, int H,
+                   int W, int k, int radius, int min_known, int iters, float tol, float* out, float* info, void* workspace,
+                   size_t workspace_bytes, void* stream);
+
 /* KITTI Eigen ground truth from raw Velodyne scans (monodepth2 kitti_utils.generate_depth_map), the forward direction of the projection
  * above: scan -> sparse depth map, per image of a batch.  The definition is tests/velo_ref.py; for image b with points p = (x, y, z, r)
  * (float32, as stored in the .bin file; r is never read), P = P[b] (3x4 velodyne -> image, float64) and true size (Hb, Wb) = sizes[b]:

@@ -8,6 +8,8 @@ preprocessing step and no .npz file.  The reference reads these scans too (geome
     P, (H, W) = velo_to_image(calib_dir)                              # host numpy, monodepth2's composition
     gt = depth_maps(points, offsets, P, sizes)                        # [B, 1, Hg, Wg] float32 on the device, zero-padded
     depth = generate_depth_map(calib_dir, velo_filename)              # monodepth2's signature: [H, W] float32 numpy
+    few = select_beams(scan, keep=(5, 7, 9, 11))                       # a 4-beam scanner out of KITTI's 64 beams (host numpy)
+    sparse = sparse_maps(points, offsets, P, sizes, h, w)             # [B, h, w]: the scans on the network's grid, for pseudo_lidar.gdc
 """
 import ctypes
 import os
@@ -90,6 +92,40 @@ def depth_maps(points, offsets, P, sizes, Hg=None, Wg=None, flip=None, depth_fro
                                       L.c_p(base + o_fl) if fl is not None else L.c_p(0), B, Hg, Wg, max_points, flags, L.ptr(out),
                                       L.stream()), "mcav_velo_depth_map")
     return out
+
+
+def select_beams(points, keep, of=64, fov=(-24.9, 2.0)):
+    """The rows of a scan that lie on the beams `keep`: elevation = atan2(z, hypot(x, y)) in degrees, float64, binned into `of` equal bins
+    over fov = (lowest, highest) (bin = floor((elevation - lowest) / (highest - lowest) * of); bin 0 is the lowest beam); rows outside
+    the field of view or with a NaN belong to no beam.  Host, numpy, deterministic; the rows stay in order.  It emulates a cheap 4-beam
+    scanner from KITTI's 64-beam HDL-64E scans (Pseudo-LiDAR++ section 5)."""
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] < 3:
+        raise L.MCAVError("select_beams: points must be [N, >= 3], got %s" % (pts.shape,))
+    of, lo, hi = int(of), float(fov[0]), float(fov[1])
+    if of < 1 or not hi > lo:
+        raise L.MCAVError("select_beams: of must be positive and fov ascending, got %r, %r" % (of, fov))
+    keep = np.unique(np.asarray(list(keep), dtype=np.int64))
+    if keep.size and (keep[0] < 0 or keep[-1] >= of):
+        raise L.MCAVError("select_beams: keep must name beams in 0..%d, got %r" % (of - 1, keep.tolist()))
+    xyz = pts[:, :3].astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        elev = np.degrees(np.arctan2(xyz[:, 2], np.hypot(xyz[:, 0], xyz[:, 1])))
+        pos = np.floor((elev - lo) / (hi - lo) * of)
+        inside = (pos >= 0) & (pos < of)
+    beam = np.where(inside, pos, -1).astype(np.int64)
+    return pts[np.isin(beam, keep) & inside]
+
+
+def sparse_maps(points, offsets, P, sizes, h, w, **kw):
+    """depth_maps on the network's h x w grid: P [B, 3, 4] is the velodyne -> image matrix at the resolutions `sizes` (B pairs (Hb, Wb));
+    its first row is scaled by w / Wb and its second by h / Hb, and every map is h x w.  -> [B, h, w] float32 on the device, 0 where no
+    point lands: the `sparse` input of pseudo_lidar.gdc."""
+    sz = np.asarray(sizes.cpu() if torch.is_tensor(sizes) else sizes, dtype=np.float64).reshape(-1, 2)
+    Pm = np.array(np.asarray(P.cpu() if torch.is_tensor(P) else P, dtype=np.float64).reshape(sz.shape[0], 3, 4))
+    Pm[:, 0, :] *= (float(w) / sz[:, 1])[:, None]
+    Pm[:, 1, :] *= (float(h) / sz[:, 0])[:, None]
+    return depth_maps(points, offsets, Pm, [(int(h), int(w))] * sz.shape[0], **kw)[:, 0]
 
 
 def generate_depth_map(calib_dir, velo_filename, cam=2, vel_depth=False):

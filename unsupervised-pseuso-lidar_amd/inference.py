@@ -9,6 +9,11 @@
     python inference.py --config C --checkpoint X --out DIR [--beams NB NA] [--scale S | --scale ground] [--max-depth D]
                         [--camera-height M] [--ground-angle DEG] [--ground-min N]
                         [--pillars [--pillar-size VX VY] [--pillar-points N] [--pillar-range X0 X1 Y0 Y1 Z0 Z1]]
+                        [--gdc [--gdc-beams 5 7 9 11] [--gdc-iters 400] [--gdc-k 10] [--gdc-radius 3]]
+
+--gdc corrects every frame's depth map against a few beams of its own Velodyne scan before the cloud is made (Pseudo-LiDAR++'s
+graph-based depth correction, pseudo_lidar.gdc): disparity -> depth (times the chosen scale, `ground` included) -> gdc against the
+scan thinned to --gdc-beams of its 64 -> project_batch(input="depth").  It needs datasets.groundtruth: velodyne.
 
 --pillars also writes out/<date>/<drive>/pseudo_pillars/data/<frame>.npz (voxels [P, N, 4], coords [P, 4] = (image in its batch, 0, iy,
 ix), num_points [P]) beside every .bin: the cloud voxelised on the GPU (pseudo_lidar.pillarize; default PointPillars' KITTI grid).
@@ -28,7 +33,7 @@ import numpy as np
 import torch
 import yaml
 
-from pseudo_lidar import PillarGrid, PseudoLiDAR, beam_tables
+from pseudo_lidar import PillarGrid, PseudoLiDAR, beam_tables, gdc as gdc_correct, ground_scale
 
 
 class Inference:
@@ -68,14 +73,52 @@ class Inference:
         return out[0] if isinstance(out, (list, tuple)) else out
 
     @torch.no_grad()
-    def clouds(self, samples, **kw):
+    def clouds(self, samples, gdc=None, **kw):
         """One batch of a datasets.calibration loader -> CloudBatch.  kw: PseudoLiDAR.project_batch's (scale -- a number, a tensor [B] or
-        "ground" with its keywords in ground={...} --, max_height, max_depth, beams, intensity, out)."""
+        "ground" with its keywords in ground={...} --, max_height, max_depth, beams, intensity, out).  gdc: None, or a dict of
+        pseudo_lidar.gdc's keywords plus `beams` (the beams of the 64 to keep of every frame's scan, default (5, 7, 9, 11)): the depth map
+        is corrected against the thinned scan before it is projected (corrected_depth)."""
         for key in ('P_rect', 'T_velo_cam', 'native_size'):
             if key not in samples:
                 raise ValueError("Inference.clouds: the batch has no %r; build the dataset with datasets.calibration: true" % key)
-        return self.projector.project_batch(self.disparity(samples['tgt']), sizes=samples['native_size'], P=samples['P_rect'],
-                                            T=samples['T_velo_cam'], **kw)
+        if gdc is None:
+            return self.projector.project_batch(self.disparity(samples['tgt']), sizes=samples['native_size'], P=samples['P_rect'],
+                                                T=samples['T_velo_cam'], **kw)
+        scale, ground = kw.pop('scale', 1.0), kw.pop('ground', None)
+        depth = self.corrected_depth(samples, gdc, scale=scale, ground=ground).depth
+        return self.projector.project_batch(depth, sizes=samples['native_size'], P=samples['P_rect'], T=samples['T_velo_cam'],
+                                            input="depth", **kw)
+
+    @torch.no_grad()
+    def corrected_depth(self, samples, gdc, scale=1.0, ground=None):
+        """disparity -> depth = scale / (10 disp + 0.01) (scale: a number, a tensor [B] or "ground" with ground={...}) -> pseudo_lidar.gdc
+        against each frame's scan thinned to gdc['beams'] and projected onto the network's grid -> GDCResult.  The scans are read from
+        <drive>/velodyne_points/data beside each frame, so the dataset must be built with datasets.groundtruth: velodyne (which checks
+        that they exist) and datasets.calibration: true."""
+        from geometry import velodyne
+        ds = self.dataset
+        if ds is None or not getattr(ds, "velodyne_gt", False) or 'path' not in samples:
+            raise ValueError("Inference: gdc needs every frame's Velodyne scan and calibration; build the dataset with "
+                             "datasets.groundtruth: velodyne and datasets.calibration: true")
+        opts = dict(gdc)
+        beams = tuple(opts.pop('beams', (5, 7, 9, 11)))
+        disp = self.disparity(samples['tgt'])[:, 0]
+        B, h, w = disp.shape
+        sizes = samples['native_size']
+        if isinstance(scale, str):
+            if scale != "ground":
+                raise ValueError("Inference: scale must be a number, a tensor [B] or 'ground', got %r" % (scale,))
+            scale = ground_scale(disp, sizes=sizes, P=samples['P_rect'], **dict(ground or {})).scales
+        depth = 1.0 / (10.0 * disp + 0.01)
+        depth = depth * (scale.to(depth.device).view(B, 1, 1) if torch.is_tensor(scale) else float(scale))
+        scans, Ps = [], []
+        for path in samples['path']:
+            scans.append(velodyne.select_beams(velodyne.load_velodyne_points(ds.resolve(ds.velodyne_scan(path))), beams))
+            Ps.append(ds.velo_calib_of(path)[0])
+        offsets = np.concatenate([[0], np.cumsum([len(s) for s in scans])]).astype(np.int64)
+        points = torch.from_numpy(np.concatenate(scans).astype(np.float32).reshape(-1, 4))
+        sparse = velodyne.sparse_maps(points, offsets, np.stack(Ps), sizes, h, w, device=self.device)
+        return gdc_correct(depth.contiguous(), sparse.contiguous(), P=samples['P_rect'], sizes=sizes, **opts)
 
     @torch.no_grad()
     def pillars(self, samples, grid=None, max_points=32, decorate=False, **cloud_kw):
@@ -150,6 +193,13 @@ def pillar_arguments(args):
     return dict(grid=PillarGrid(x=(r[0], r[1]), y=(r[2], r[3]), z=(r[4], r[5]), size=tuple(args.pillar_size)), max_points=args.pillar_points)
 
 
+def gdc_arguments(args):
+    """--gdc and its options -> clouds' `gdc` (None without the flag)"""
+    if not args.gdc:
+        return None
+    return dict(beams=tuple(args.gdc_beams), iters=args.gdc_iters, k=args.gdc_k, radius=args.gdc_radius)
+
+
 def build_parser():
     ap = argparse.ArgumentParser(description="checkpoint + KITTI split -> pseudo-LiDAR .bin clouds")
     ap.add_argument("--config", required=True)
@@ -167,19 +217,33 @@ def build_parser():
     ap.add_argument("--pillar-points", type=int, default=32, help="--pillars: the points kept per pillar (1..64), the first in cloud order")
     ap.add_argument("--pillar-range", nargs=6, type=float, default=(0.0, 69.12, -39.68, 39.68, -3.0, 1.0),
                     metavar=("X0", "X1", "Y0", "Y1", "Z0", "Z1"), help="--pillars: the grid's extent in the velodyne frame, metres")
+    ap.add_argument("--gdc", action="store_true",
+                    help="correct every depth map against a few beams of the frame's Velodyne scan (needs datasets.groundtruth: velodyne)")
+    ap.add_argument("--gdc-beams", nargs="+", type=int, default=(5, 7, 9, 11), help="--gdc: the beams of the scan's 64 that are kept")
+    ap.add_argument("--gdc-iters", type=int, default=400, help="--gdc: conjugate-gradient iterations at most")
+    ap.add_argument("--gdc-k", type=int, default=10, help="--gdc: neighbours per pixel (1..16)")
+    ap.add_argument("--gdc-radius", type=int, default=3, help="--gdc: the neighbours come from a (2 r + 1)^2 pixel window (1..7)")
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     pillars = pillar_arguments(args)
+    gdc = gdc_arguments(args)
     with open(args.config) as f:
         config = yaml.full_load(f)
+    if gdc is not None:
+        ds = config.get('datasets', {})
+        if ds.get('groundtruth') != 'velodyne' or not ds.get('calibration'):
+            raise ValueError("--gdc needs every frame's Velodyne scan and calibration: set datasets.groundtruth: velodyne and "
+                             "datasets.calibration: true in %s" % args.config)
     kw = dict(scale=args.scale, max_depth=args.max_depth)
     if args.scale == "ground":
         kw["ground"] = dict(camera_height=args.camera_height, max_angle_deg=args.ground_angle, min_ground=args.ground_min)
     if args.beams:
         kw["beams"] = beam_tables(args.beams[0], args.beams[1])
+    if gdc is not None:
+        kw["gdc"] = gdc
     n = Inference(config, args.checkpoint).export(args.out, pillars=pillars, **kw)
     print("wrote %d clouds%s under %s" % (n, " and their pillars" if pillars is not None else "", args.out))
 

@@ -19,6 +19,11 @@ tests/ground_scale_ref.py).  `project_batch(..., scale="ground")` runs it and ha
 `pillarize(points, offsets)` / `CloudBatch.pillars()` turn a cloud batch into what a LiDAR 3-D detector reads (PointPillars / SECOND /
 OpenPCDet): a `PillarBatch` of voxels [P, N, C], coords [P, 4] = (batch, z, y, x) and num_points [P] on a `PillarGrid`, the first N points
 of every non-empty cell in cloud order (mcav_pillarize; the definition is tests/pillar_ref.py).  Still nothing is read back.
+
+`gdc(depth, sparse, K)` is Pseudo-LiDAR++'s graph-based depth correction: a few exact LiDAR depths (a 4-beam scanner's, as a sparse map
+on the prediction's grid: geometry.velodyne.sparse_maps) are propagated over the predicted depth map along a windowed KNN graph of its
+back-projected pixels, keeping the predicted local shape (mcav_gdc_graph, mcav_gdc_solve; the definition is tests/gdc_ref.py).  The
+corrected map goes into project_batch(input="depth").
 """
 import ctypes
 
@@ -42,6 +47,9 @@ L.register({
     "mcav_pillarize_workspace_bytes": (L.c_sz, [L.c_i, ctypes.c_longlong, L.c_i, L.c_i]),
     "mcav_pillarize": (L.c_i, [L.c_p, L.c_p, L.c_i, ctypes.c_longlong] + [L.c_f] * 6 + [L.c_i] * 4 + [L.c_p] * 3 + [ctypes.c_longlong, L.c_p,
                                L.c_p, L.c_sz, L.c_p]),
+    "mcav_gdc_workspace_bytes": (L.c_sz, [L.c_i] * 5),
+    "mcav_gdc_graph": (L.c_i, [L.c_p] * 3 + [L.c_i] * 5 + [L.c_f] * 3 + [L.c_p] * 4 + [L.c_sz, L.c_p]),
+    "mcav_gdc_solve": (L.c_i, [L.c_p] * 5 + [L.c_i] * 7 + [L.c_f] + [L.c_p] * 3 + [L.c_sz, L.c_p]),
 })
 
 PLB_INPUT_DEPTH = 1                            # include/mcav_depth.h MCAV_PLB_INPUT_DEPTH
@@ -352,6 +360,89 @@ def ground_scale(m, sizes=None, P=None, camera_height=1.65, max_angle_deg=5.0, b
                                      float(camera_height), cos_max, int(min_ground), float(fallback),
                                      GS_INPUT_DEPTH if input == "depth" else 0, L.ptr(out.rows), L.ptr(out.mask if keep_mask else None),
                                      L.ptr(out._ws), out._ws.numel(), L.stream()), "mcav_ground_scale")
+    return out
+
+
+class GDCResult:
+    """gdc's result, on the device: `depth` [B, h, w] float32, the corrected map; `info` [B, 4] float32 = (graph pixels, known graph
+    pixels, iterations run, rs / rs0) per image; `graph`: with keep_graph the graph it was solved on, (nbr, weights, flags), else None.
+    The object owns the graph's buffers either way (a later call with out= reuses them): `nbr` int32 [B, h, w, k] (pixel index or -1),
+    `weights` float32 [B, h, w, k], `flags` uint8 [B, h, w] (bit 0: in the graph, bit 1: known).  Nothing is read back."""
+
+    def __init__(self, batch, h, w, k, device):
+        self.depth = torch.empty((int(batch), int(h), int(w)), dtype=torch.float32, device=device)
+        self.info = torch.empty((int(batch), 4), dtype=torch.float32, device=device)
+        self.nbr = torch.empty((int(batch), int(h), int(w), int(k)), dtype=torch.int32, device=device)
+        self.weights = torch.empty((int(batch), int(h), int(w), int(k)), dtype=torch.float32, device=device)
+        self.flags = torch.empty((int(batch), int(h), int(w)), dtype=torch.uint8, device=device)
+        self.graph = None
+        self._ws, self._K_bytes, self._K = None, None, None
+
+
+def grid_intrinsics(P, sizes, h, w):
+    """P [B, 3, 4] (or [3, 4]) at the resolutions `sizes` (B pairs (Hb, Wb)) -> float32 [B, 4] = (fx, fy, cx, cy) on an h x w grid: row 0
+    times w / Wb, row 1 times h / Hb, as project_batch rescales its calibration."""
+    sz = np.asarray(sizes.cpu() if torch.is_tensor(sizes) else sizes, dtype=np.float64).reshape(-1, 2)
+    Pm = _matrices(P, sz.shape[0], (3, 4), "gdc: P")
+    sx, sy = float(w) / sz[:, 1], float(h) / sz[:, 0]
+    return np.stack([Pm[:, 0, 0] * sx, Pm[:, 1, 1] * sy, Pm[:, 0, 2] * sx, Pm[:, 1, 2] * sy], axis=1).astype(np.float32)
+
+
+def gdc(depth, sparse, K=None, k=10, radius=3, reg=1e-3, min_depth=1e-3, max_depth=80.0, min_known=1, iters=400, tol=1e-4, out=None,
+        keep_graph=False, P=None, sizes=None):
+    """Graph-based depth correction from sparse LiDAR (Pseudo-LiDAR++; mcav_gdc_graph + mcav_gdc_solve).
+    depth: [B, h, w] or [B, 1, h, w] float32 on the GPU, the predicted metric depth; sparse: the same shape, exact depths, 0 where there
+    is none; K: [B, 4] or [4] = (fx, fy, cx, cy) of that grid (host values or a float32 tensor on the GPU), or P [B, 3, 4] / [3, 4] with
+    sizes (B pairs (Hb, Wb), default (h, w)): the rows are rescaled to the grid.  k: neighbours (1..16) within a (2 radius + 1)^2 window
+    (radius 1..7); reg: the ridge of the weights; a pixel counts iff min_depth < depth <= max_depth; an image with fewer than min_known
+    known pixels passes through unchanged; at most iters conjugate-gradient iterations, an image stops once |r|^2 <= tol^2 |r0|^2.
+    out: a GDCResult to reuse with its workspace (needed under graph capture); keep_graph: the result's `.graph` holds (nbr, weights,
+    flags).  -> GDCResult; no host synchronisation."""
+    depth, sparse = _plane(depth, "gdc"), _plane(sparse, "gdc")
+    if depth.shape != sparse.shape or depth.device != sparse.device:
+        raise L.MCAVError("gdc: depth and sparse must have one shape and device, got %s and %s" % (tuple(depth.shape), tuple(sparse.shape)))
+    B, h, w = depth.shape
+    k, radius = int(k), int(radius)
+    if not 1 <= k <= 16 or not 1 <= radius <= 7:
+        raise L.MCAVError("gdc: k must be in 1..16 and radius in 1..7, got %r and %r" % (k, radius))
+    if int(iters) < 0 or not float(tol) >= 0.0 or not float(reg) > 0.0:
+        raise L.MCAVError("gdc: iters and tol must not be negative and reg must be positive, got %r, %r, %r" % (iters, tol, reg))
+    if (K is None) == (P is None):
+        raise L.MCAVError("gdc: give K (fx, fy, cx, cy of the grid) or P with sizes, not both")
+    dev = depth.device
+    if out is None:
+        out = GDCResult(B, h, w, k, dev)
+    elif not isinstance(out, GDCResult) or tuple(out.nbr.shape) != (B, h, w, k) or out.depth.device != dev:
+        raise L.MCAVError("gdc: out must be a GDCResult of [%d, %d, %d] with k = %d on %s" % (B, h, w, k, dev))
+    if torch.is_tensor(K) and K.is_cuda:
+        if tuple(K.shape) != (B, 4):
+            raise L.MCAVError("gdc: a K tensor on the GPU must be [%d, 4], got %s" % (B, tuple(K.shape)))
+        Kd = L.dev(K, "K")
+    else:
+        try:
+            Kh = grid_intrinsics(P, _sizes(sizes, B, h, w, "gdc"), h, w) if K is None else \
+                np.ascontiguousarray(np.broadcast_to(np.asarray(K.cpu() if torch.is_tensor(K) else K, dtype=np.float32), (B, 4)))
+        except ValueError:
+            raise L.MCAVError("gdc: K must be [4] or [%d, 4]" % B)
+        if out._K_bytes != Kh.tobytes():              # as project_batch: a second call with the same calibration copies nothing
+            out._K = torch.from_numpy(Kh.copy()).pin_memory().to(dev, non_blocking=True)
+            out._K_bytes = Kh.tobytes()
+        Kd = out._K
+    hl = L.lib()
+    nbytes = hl.mcav_gdc_workspace_bytes(B, h, w, k, radius)
+    if nbytes == 0:
+        raise L.MCAVError("gdc: a batch of %d x %d x %d pixels with k = %d is refused (h w <= 2^24, k B h w < 2^31)" % (B, h, w, k))
+    if out._ws is None or out._ws.numel() < nbytes:
+        out._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        L.check(hl.mcav_gdc_graph(L.ptr(depth), L.ptr(sparse), L.ptr(Kd), B, h, w, k, radius, float(reg), float(min_depth), float(max_depth),
+                                  L.ptr(out.nbr), L.ptr(out.weights), L.ptr(out.flags), L.ptr(out._ws), out._ws.numel(), L.stream()),
+                "mcav_gdc_graph")
+        L.check(hl.mcav_gdc_solve(L.ptr(depth), L.ptr(sparse), L.ptr(out.nbr), L.ptr(out.weights), L.ptr(out.flags), B, h, w, k, radius,
+                                  int(min_known), int(iters), float(tol), L.ptr(out.depth), L.ptr(out.info), L.ptr(out._ws),
+                                  out._ws.numel(), L.stream()), "mcav_gdc_solve")
+    out._inputs = (depth, sparse, Kd)                 # alive as long as the enqueued work may read them
+    out.graph = (out.nbr, out.weights, out.flags) if keep_graph else None
     return out
 
 

@@ -1,2 +1,2 @@
-from .PseudoLiDAR import (BeamTables, CloudBatch, GroundScale, PillarBatch, PillarGrid, PseudoLiDAR, beam_tables, ground_scale,  # noqa: F401
-                          pillarize)
+from .PseudoLiDAR import (BeamTables, CloudBatch, GDCResult, GroundScale, PillarBatch, PillarGrid, PseudoLiDAR, beam_tables,  # noqa: F401
+                          gdc, ground_scale, pillarize)
