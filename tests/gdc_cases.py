@@ -14,6 +14,9 @@ exists because the kernels can go wrong there:
     holes      NaN / +inf / 0 / beyond max_depth in blocks wider than the window: pixels with fewer than k candidates, isolated valid
                pixels that leave the graph, a known pixel on an invalid prediction, sparse values outside the range
     mixed      B = 3: the scene, an image without any known pixel, an image below min_known (= 3, with two known pixels)
+SCAN_CASES, a list of its own (the GPU tests take it; the CPU suites' transcriptions and dense solves do not):
+    chunks     128 x 516, B = 1: 258 workgroups of 256 pixels, more than the 256 block sums that the one-block scan takes per pass, so
+               the CSR row starts of the last two workgroups carry the first pass's total
 """
 import functools
 
@@ -23,6 +26,7 @@ import gdc_ref as R
 
 F = np.float32
 CASES = ["scene", "odd", "full", "wide", "k1", "k16", "r1", "wall", "holes", "mixed"]
+SCAN_CASES = ["chunks"]
 HARDEST = "holes"
 
 
@@ -92,6 +96,8 @@ def build(case):
         assert np.isnan(depth[0, 9, 4])
         sparse[1, 9, 2:30:4] = [np.nan, np.inf, 500.0, -1.0, 1e-4, 80.0, 80.00001]       # outside the range, but for the 80.0
         sparse[1, 3, 3] = 5.0                                           # on a 0 prediction
+    elif case == "chunks":
+        truth, depth, sparse, K = batch([(0.0, 71)], 128, 516)
     elif case == "mixed":
         min_known = 3
         truth, depth, sparse, K = batch([(0.0, 61), (0.5, 62), (1.0, 63)], 24, 40)
@@ -175,3 +181,7 @@ def check_non_trivial(case):
         assert (used[in_graph] == k).all()
     if case == "mixed":
         assert [int((in_graph[b] & known[b]).sum()) for b in range(3)][1:] == [0, 2]
+    if case == "chunks":
+        B, H, W = fl.shape
+        assert B * ((H * W + 255) // 256) > 256                        # B * G workgroups: a second pass of the block-sum scan
+        assert in_graph[0].reshape(-1)[256 * 256:].any() and (in_graph & known).sum() > 1000

@@ -8,6 +8,12 @@ and upper edges, all shuffled.  Shapes (B = 3):
     mixed : populated, no rows at all, every row outside the grid;      50 unused rows of in-range values behind offsets[B]
     pair  : populated, populated (another seed), no rows;               the same padding
     over  : as pair, with offsets[B] 37 rows beyond n_max: the cloud buffer was too small, the last image is cut
+TILE_CASES, a list of its own (the GPU tests take it; the CPU suites' sequential transcription does not):
+    tiles : B = 5 on PointPillars' own 432 x 496 grid: 1 071 360 cells = 1047 tiles of 1024 cells, more than the 1024 tile sums that the
+            one-block scan takes per pass, and ny * nx is no multiple of 1024, so image boundaries fall inside tiles.  600 uniform
+            in-range points per image, N = 4, 4 columns: nearly every pillar stands in a tile of its own, each offset by the tiles before.
+            (test_pillar_gpu.py's test_scan_past_its_first_pass reaches the same second pass with dense random clouds and decorated
+            columns; this case keeps the shape among the shared cases, with its properties asserted by check_non_trivial.)
 """
 import functools
 
@@ -23,6 +29,8 @@ SHAPES = ("mixed", "pair", "over")
 CASES = ["mixed-N%d-c%d" % (n, c) for n in POINTS for c in (4, 9)] + ["pair-N5-c9", "pair-N32-c4", "over-N4-c9", "over-N64-c4"]
 HARDEST = "over-N5-c9"                                       # chunks, a cut image, the decorated columns, a block that starts off 16 bytes
 CASES.append(HARDEST)
+TILE_CASES = ["tiles"]
+TILE = 1024                                                  # cells per workgroup of the scan passes (csrc/pillarize.hip)
 
 
 def planted_counts(N):
@@ -72,6 +80,15 @@ def outside_points(seed):
 @functools.lru_cache(maxsize=None)
 def build(case):
     """-> dict(points [n_max, 4], offsets int32 [B + 1], grid, max_points, decorate)"""
+    if case == "tiles":
+        g, B, per = R.make_grid(x=(0.0, 69.12), y=(-39.68, 39.68), z=(-3.0, 1.0), size=(0.16, 0.16)), 5, 600
+        rng = np.random.RandomState(77)
+        pts = np.stack([rng.uniform(0.0, 69.12, B * per), rng.uniform(-39.68, 39.68, B * per), rng.uniform(-3.0, 1.0, B * per),
+                        rng.rand(B * per)], axis=1).astype(F)
+        offsets = (np.arange(B + 1) * per).astype(np.int32)
+        pts.setflags(write=False)
+        offsets.setflags(write=False)
+        return dict(points=pts, offsets=offsets, grid=g, max_points=4, decorate=False)
     shape, n, c = case.split("-")
     N, seed = int(n[1:]), 100 * SHAPES.index(shape)
     empty = np.zeros((0, 4), F)
@@ -102,6 +119,13 @@ def reference(case):
 def check_non_trivial(case):
     """the planted cells came out as planted, both populated images have pillars, the padding rows would have added pillar points"""
     a, want = build(case), reference(case)
+    if case == "tiles":
+        g, c = a["grid"], want["coords"].astype(np.int64)
+        cell = (c[:, 0] * g.ny + c[:, 2]) * g.nx + c[:, 3]                                 # flat over (image, iy, ix), as the kernels count
+        assert (cell >= 1 << 20).any()                                                     # beyond the first pass of the tile scan
+        assert len(np.unique(cell[cell < 1 << 20] // TILE)) >= 3                           # cross-tile offsets inside the first pass
+        assert g.ny * g.nx % TILE != 0                                                     # an image boundary inside a tile
+        return
     N = a["max_points"]
     P = int(want["offsets"][-1])
     assert P == len(want["coords"]) >= 40

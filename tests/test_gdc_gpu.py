@@ -83,8 +83,7 @@ def bits(x):
     return np.ascontiguousarray(x).view(np.uint32)
 
 
-@pytest.mark.parametrize("case", C.CASES)
-def test_graph_matches_restatement_bit_for_bit(case):
+def check_graph(case):
     C.check_non_trivial(case)
     a, buf = buffers_for(case)
     buf.graph(a)
@@ -97,6 +96,11 @@ def test_graph_matches_restatement_bit_for_bit(case):
     assert bool((buf.out == -77.0).all())                    # the graph call writes no other output
 
 
+@pytest.mark.parametrize("case", C.CASES)
+def test_graph_matches_restatement_bit_for_bit(case):
+    check_graph(case)
+
+
 def solver_bound(case, iters):
     """4 x (float32 restatement against float64 arithmetic on the same graph) + 1e-6 m, over the finite pixels"""
     x, y = C.solved32(case, iters)[0], C.solved64(case, iters)[0]
@@ -105,15 +109,14 @@ def solver_bound(case, iters):
     return measured, 4 * measured + 1e-6
 
 
-@pytest.mark.parametrize("case", C.CASES)
-def test_solver_matches_restatement(case):
-    """iters = 0: the start vector's bits.  iters in {1, 2, 5}: the restatement within the bound; known pixels, pixels off the graph and
+def check_solver(case, counts):
+    """iters = 0: the start vector's bits.  iters > 0: the restatement within the bound; known pixels, pixels off the graph and
     passed-through images bit for bit at every count; info exact; sentinels and the workspace's neighbours untouched."""
     a, buf = buffers_for(case)
     buf.graph(a)
     fl = C.graph32(case)[2]
     off, known = (fl & 1) == 0, (fl & 3) == 3
-    for iters in (0, 1, 2, 5):
+    for iters in counts:
         buf.solve(a, iters)
         _, _, _, out, info = buf.results()
         want, winfo = C.solved32(case, iters)
@@ -138,6 +141,19 @@ def test_solver_matches_restatement(case):
             assert err <= bound
             assert np.allclose(info[:, 3], winfo[:, 3], rtol=1e-3, atol=0)
         buf.sentinels_intact()
+
+
+@pytest.mark.parametrize("case", C.CASES)
+def test_solver_matches_restatement(case):
+    check_solver(case, (0, 1, 2, 5))
+
+
+@pytest.mark.parametrize("case", C.SCAN_CASES)
+def test_more_block_sums_than_one_scan_pass(case):
+    """258 workgroups: the scan of the per-workgroup in-degree sums takes a second pass and carries the first one's total into the CSR
+    row starts, which the transposed product reads.  The graph bit for bit, the solver at 0 and 2 iterations under its bound."""
+    check_graph(case)
+    check_solver(case, (0, 2))
 
 
 def test_400_iterations_against_the_dense_float64_solution():

@@ -78,6 +78,14 @@ def test_kernels_match_restatement(case):
         assert np.array_equal(c.cpu().numpy(), want["coords"][lo:hi]) and np.array_equal(k.cpu().numpy(), want["num_points"][lo:hi])
 
 
+@pytest.mark.parametrize("case", C.TILE_CASES)
+def test_more_tiles_than_one_scan_pass(case):
+    """1047 tiles of 1024 cells: the scan of the tile sums takes a second pass with a carry, and every tile but the first starts its
+    segments and pillar ranks at the sums of the tiles before it"""
+    C.check_non_trivial(case)
+    check(run(C.build(case)), C.reference(case))
+
+
 @pytest.mark.parametrize("case", ["pair-N5-c9", "over-N64-c4"])
 def test_capacity_below_the_count(case):
     """offsets stay exact, the rows that fit are written, nothing behind them is touched -- in buffers that go on behind the capacity"""

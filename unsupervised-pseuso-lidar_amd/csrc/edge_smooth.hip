@@ -14,7 +14,7 @@
 
 #include "edge_math.h"
 #include "kernel_timer.h"
-#include "mcav_common.h"
+#include "block_ops.h"
 
 namespace mcav {
 
@@ -36,16 +36,6 @@ struct ESArgs {
     double* slab_r;            // [B][G]
     double* sample_e;          // [B]
 };
-
-// sum over the 256 threads in a fixed order; thread 0 gets the total (s: 4 doubles of LDS)
-__device__ __forceinline__ double block_sum_d(double v, double* s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();                                   // s may still be read from a previous call
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s[0] + s[1]) + s[2]) + s[3];
-}
 
 // UNIT: f == 1, the image taps are plain loads
 template <bool UNIT>
@@ -70,41 +60,33 @@ __global__ __launch_bounds__(ES_THREADS) void edge_smooth_fwd_kernel(ESArgs a) {
         sd += p < n ? dq : 0.f;
         sr += p < n ? v : 0.f;
     }
-    const double bm = block_sum_d((double)sd, s_red);
-    const double br = block_sum_d((double)sr, s_red);
+    const double bm = block_sum<double, ES_THREADS / 64>((double)sd, s_red);
+    const double br = block_sum<double, ES_THREADS / 64>((double)sr, s_red);
     const size_t slot = (size_t)b * a.G + blockIdx.x;
     if (tid == 0) {
         handoff_store(a.slab_m + slot, bm);
         handoff_store(a.slab_r + slot, br);
     }
-    handoff_release();                                 // the slab stores have been acknowledged ...
-    __syncthreads();
-    if (tid == 0) s_flag = handoff_ticket(&a.tickets[b]) == (unsigned)(a.G - 1);      // ... before the ticket is taken
-    __syncthreads();
-    if (!s_flag) return;
+    if (!handoff_last([&] { return &a.tickets[b]; }, a.G, &s_flag)) return;
     // the last workgroup of sample b: its slab entries in a fixed order (thread t takes entries t, t + 256, ...)
     double tm = 0.0, tr = 0.0;
     for (int i = tid; i < a.G; i += ES_THREADS) {
         tm += handoff_load(a.slab_m + (size_t)b * a.G + i);
         tr += handoff_load(a.slab_r + (size_t)b * a.G + i);
     }
-    const double m = block_sum_d(tm, s_red) / (double)n;
-    const double R = block_sum_d(tr, s_red);
+    const double m = block_sum<double, ES_THREADS / 64>(tm, s_red) / (double)n;
+    const double R = block_sum<double, ES_THREADS / 64>(tr, s_red);
     if (tid == 0) {
         handoff_store(a.saved + b, m);
         handoff_store(a.saved + a.B + b, R);
         handoff_store(a.sample_e + b, es::sample_loss(m, R));
         handoff_store(&a.tickets[b], 0u);
     }
-    handoff_release();
-    __syncthreads();
-    if (tid == 0) s_flag = handoff_ticket(&a.tickets[a.B]) == (unsigned)(a.B - 1);
-    __syncthreads();
-    if (!s_flag) return;
+    if (!handoff_last([&] { return &a.tickets[a.B]; }, a.B, &s_flag)) return;
     // the last sample: every E_b, added in a fixed order (thread t takes samples t, t + 256, ...)
     double e = 0.0;
     for (int i = tid; i < a.B; i += ES_THREADS) e += handoff_load(a.sample_e + i);
-    e = block_sum_d(e, s_red);
+    e = block_sum<double, ES_THREADS / 64>(e, s_red);
     if (tid == 0) {
         a.loss_accum[0] += (float)((double)a.weight * e);
         handoff_store(&a.tickets[a.B], 0u);

@@ -18,7 +18,7 @@
 
 #include "eval_math.h"
 #include "kernel_timer.h"
-#include "mcav_common.h"
+#include "block_ops.h"
 
 namespace mcav {
 
@@ -27,10 +27,7 @@ constexpr int EV_PPT = 8;                              // gather / metrics: pixe
 constexpr int EV_TILE = EV_THREADS * EV_PPT;           // crop-box pixels per workgroup
 constexpr int EV_KPT = 16;                             // hist: keys per thread
 constexpr int EV_KTILE = EV_THREADS * EV_KPT;          // keys per workgroup
-constexpr int EV_BINS = 2048;
-constexpr int EV_PASSES = 3;
-__constant__ const int ev_shift[EV_PASSES] = {21, 10, 0};
-__constant__ const int ev_width[EV_PASSES] = {11, 11, 10};
+constexpr int EV_BINS = RADIX_BINS;
 
 struct EVBox {
     int y0, y1, x0, x1;      // half-open, inside the true size, inside the padded size
@@ -170,9 +167,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_hist_kernel(EVArgs a, int p) 
     if (start >= n) return;                            // uniform over the workgroup
     for (int i = tid; i < 2 * EV_BINS; i += EV_THREADS) (&lh[0][0])[i] = 0u;
     __syncthreads();
-    const int shift = ev_shift[p], top = shift + ev_width[p];
-    const unsigned dmask = (1u << ev_width[p]) - 1u;
-    const unsigned pmask = top >= 32 ? 0u : ~0u << top;
+    const auto [shift, dmask, pmask] = radix_pass(p);
     const unsigned* st = a.state + ((size_t)b * 2 + buf) * 4;
     const unsigned pre0 = p ? st[0] & pmask : 0u, pre1 = p ? st[2] & pmask : 0u;
     const unsigned* kb = a.keys + ((size_t)b * 2 + buf) * ev_plane(a);
@@ -198,39 +193,21 @@ __global__ __launch_bounds__(EV_THREADS) void eval_hist_kernel(EVArgs a, int p) 
 __global__ __launch_bounds__(EV_THREADS) void eval_select_kernel(EVArgs a, int p) {
     __shared__ unsigned wtot[EV_THREADS / 64];
     constexpr int PER = EV_BINS / EV_THREADS;          // 8 bins per thread
-    const int buf = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int buf = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const unsigned n = a.meta[2 * b];
     if (n == 0) return;                                // nothing was counted: the histogram is still zero
     unsigned* hg = a.hist + ((size_t)b * 2 + buf) * 2 * EV_BINS;
     unsigned* st = a.state + ((size_t)b * 2 + buf) * 4;
-    const int shift = ev_shift[p];
-    unsigned c[2][PER], pick[2] = {0u, 0u}, left[2] = {0u, 0u};
-    bool mine[2] = {false, false};
+    const int shift = radix_pass(p).shift;
+    unsigned pick[2] = {0u, 0u}, left[2] = {0u, 0u};
+    bool mine[2];
     for (int r = 0; r < 2; ++r) {
         const unsigned* src = hg + (size_t)(p ? r : 0) * EV_BINS + tid * PER;
-        unsigned s = 0;
+        unsigned c[PER];
 #pragma unroll
-        for (int j = 0; j < PER; ++j) { c[r][j] = src[j]; s += c[r][j]; }
-        unsigned v = s;                                // inclusive scan over the wave, then over the four waves
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const unsigned t = __shfl_up(v, off, 64);
-            if (lane >= off) v += t;
-        }
-        __syncthreads();
-        if (lane == 63) wtot[wave] = v;
-        __syncthreads();
-        unsigned excl = v - s;
-        for (int w = 0; w < wave; ++w) excl += wtot[w];
+        for (int j = 0; j < PER; ++j) c[j] = src[j];
         const unsigned k = p ? st[2 * r + 1] : (r == 0 ? (n - 1) / 2 : n / 2);
-        if (k >= excl && k < excl + s) {
-            unsigned before = excl;
-            int j = 0;
-            while (before + c[r][j] <= k) before += c[r][j++];
-            mine[r] = true;
-            pick[r] = (unsigned)(tid * PER + j);
-            left[r] = k - before;
-        }
+        mine[r] = pick_bin<PER, EV_THREADS / 64>(c, k, wtot, pick[r], left[r]);
     }
     __syncthreads();                                   // every thread has read the state and the bins
     for (int r = 0; r < 2; ++r)
@@ -239,16 +216,6 @@ __global__ __launch_bounds__(EV_THREADS) void eval_select_kernel(EVArgs a, int p
             st[2 * r + 1] = left[r];
         }
     for (int i = tid; i < 2 * EV_BINS; i += EV_THREADS) hg[i] = 0u;
-}
-
-// sum over the 256 threads in a fixed order; every thread gets the total (s: 4 doubles of LDS)
-__device__ __forceinline__ double ev_block_sum(double v, double* s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s[0] + s[1]) + s[2]) + s[3];
 }
 
 __global__ __launch_bounds__(EV_THREADS) void eval_metrics_kernel(EVArgs a) {
@@ -280,7 +247,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_metrics_kernel(EVArgs a) {
     double* out = a.slab + ((size_t)b * a.G + blockIdx.x) * ev::NSUM;
 #pragma unroll
     for (int k = 0; k < ev::NSUM; ++k) {
-        const double t = ev_block_sum(s[k], s_red);
+        const double t = block_sum<double, EV_THREADS / 64>(s[k], s_red);
         if (tid == 0) out[k] = t;
     }
 }
@@ -297,7 +264,7 @@ __global__ __launch_bounds__(EV_THREADS) void eval_finalize_kernel(EVArgs a) {
         for (int k = 0; k < ev::NSUM; ++k) s[k] += src[k];
     }
 #pragma unroll
-    for (int k = 0; k < ev::NSUM; ++k) s[k] = ev_block_sum(s[k], s_red);
+    for (int k = 0; k < ev::NSUM; ++k) s[k] = block_sum<double, EV_THREADS / 64>(s[k], s_red);
     if (tid == 0) {
         float m[9];
         ev::metrics_row(s, m);
@@ -369,7 +336,7 @@ MCAV_EXPORT int mcav_eval_depth_scaled(const float* gt, const float* disp, int B
     if (flags & MCAV_EVAL_MEDIAN_SCALING) {            // without scaling no median is needed: metrics + finalize only
         timed_launch(eval_init_kernel, dim3(B), dim3(EV_THREADS), 0, s, a);
         timed_launch(eval_gather_kernel, dim3(l.G, B), dim3(EV_THREADS), 0, s, a);
-        for (int p = 0; p < EV_PASSES; ++p) {
+        for (int p = 0; p < RADIX_PASSES; ++p) {
             timed_launch(eval_hist_kernel, dim3(kg, 2, B), dim3(EV_THREADS), 0, s, a, p);
             timed_launch(eval_select_kernel, dim3(2, B), dim3(EV_THREADS), 0, s, a, p);
         }

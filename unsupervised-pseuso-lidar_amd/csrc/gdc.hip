@@ -19,13 +19,13 @@
 //   no float atomics, no allocation: the call can be captured, and two runs give the same bytes.
 #include <type_traits>
 
-#include "mcav_common.h"
+#include "block_ops.h"
 #include "gdc_math.h"
 
 namespace mcav {
 namespace gdc {
 
-constexpr int TILE = 16, THREADS = 256;
+constexpr int TILE = 16, THREADS = 256, WAVES = THREADS / 64;
 constexpr int SPAN = TILE + 2 * MAX_RADIUS;              // 30: the tile and its widest halo
 
 // ------------------------------------------------------------------------------------------------------------------- the graph
@@ -110,39 +110,6 @@ struct Solve {
     float* r; float* p; float* q;                         // [B H W]
 };
 
-// sum over the 256 threads in a fixed order; every thread gets the total (s: 4 entries of LDS)
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();                                      // s may still be read from a previous call
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s[0] + s[1]) + s[2]) + s[3];
-}
-
-// exclusive scan over the 256 threads; total: the block's sum
-__device__ __forceinline__ int block_scan(int v, int* s, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int a = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += a;
-    }
-    __syncthreads();
-    if (lane == 63) s[wave] = inc;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < THREADS / 64; ++w) {
-        if (w < wave) before += s[w];
-        total += s[w];
-    }
-    return before + inc - v;
-}
-
 // The sources that list pixel j of image b, in raster (ascending index) order: f(source, slot) for each.
 template <typename Fn>
 __device__ __forceinline__ void for_each_source(const Solve& a, int b, int j, Fn f) {
@@ -166,9 +133,9 @@ __global__ __launch_bounds__(THREADS) void gdc_count_kernel(Solve a) {
     if (i < n) fl = a.flags[(size_t)b * n + i];
     if (fl & IN_GRAPH) for_each_source(a, b, i, [&](int, int) { ++degree; });
     a.row_start[((size_t)b * a.G + blockIdx.x) * THREADS + tid] = degree;
-    const int graph = block_sum<int>((fl & IN_GRAPH) ? 1 : 0, s_red);
-    const int known = block_sum<int>((fl & (IN_GRAPH | KNOWN)) == (IN_GRAPH | KNOWN) ? 1 : 0, s_red);
-    const int total = block_sum<int>(degree, s_red);
+    const int graph = block_sum<int, WAVES>((fl & IN_GRAPH) ? 1 : 0, s_red);
+    const int known = block_sum<int, WAVES>((fl & (IN_GRAPH | KNOWN)) == (IN_GRAPH | KNOWN) ? 1 : 0, s_red);
+    const int total = block_sum<int, WAVES>(degree, s_red);
     if (tid == 0) {
         if (graph) atomicAdd(a.counts + 2 * b, graph);
         if (known) atomicAdd(a.counts + 2 * b + 1, known);
@@ -180,16 +147,8 @@ __global__ __launch_bounds__(THREADS) void gdc_count_kernel(Solve a) {
 __global__ __launch_bounds__(THREADS) void gdc_scan_kernel(Solve a) {
     __shared__ int s_red[4];
     const int nblocks = a.B * a.G;
-    int carry = 0;
-    for (int base = 0; base < nblocks; base += THREADS) {
-        const int i = base + threadIdx.x;
-        const int v = i < nblocks ? a.block_sum[i] : 0;
-        int total;
-        const int ex = block_scan(v, s_red, total);
-        if (i < nblocks) a.block_sum[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) a.row_start[(size_t)nblocks * THREADS] = carry;
+    const int total = chunked_scan<int, WAVES>(nblocks, s_red, [&](int i) { return a.block_sum[i]; }, [&](int i, int v) { a.block_sum[i] = v; });
+    if (threadIdx.x == 0) a.row_start[(size_t)nblocks * THREADS] = total;
 }
 
 __global__ __launch_bounds__(THREADS) void gdc_fill_kernel(Solve a) {
@@ -198,7 +157,7 @@ __global__ __launch_bounds__(THREADS) void gdc_fill_kernel(Solve a) {
     const size_t slot = ((size_t)b * a.G + blockIdx.x) * THREADS + tid;
     const int degree = a.row_start[slot];
     int total;
-    int at = a.block_sum[b * a.G + blockIdx.x] + block_scan(degree, s_red, total);
+    int at = a.block_sum[b * a.G + blockIdx.x] + block_scan<int, WAVES>(degree, s_red, total);
     a.row_start[slot] = at;
     if (degree == 0 || i >= n) return;
     const size_t image = (size_t)b * n;
@@ -232,28 +191,24 @@ constexpr int GROUP = 16;
 
 __device__ __forceinline__ bool image_total(const Solve& a, int b, double mine, double* s_red, int* s_flag, double& sum) {
     const int tid = threadIdx.x;
-    const double part = block_sum<double>(mine, s_red);
+    const double part = block_sum<double, WAVES>(mine, s_red);
     if (tid == 0) handoff_store(a.slab + (size_t)b * a.G + blockIdx.x, part);
-    handoff_release();                                    // the slab store has been acknowledged ...
+    handoff_release();                                    // handoff_last's steps, with the group's arithmetic behind the wait as before
     __syncthreads();
     const int groups = (a.G + GROUP - 1) / GROUP, g = blockIdx.x / GROUP, first = g * GROUP, members = min(GROUP, a.G - first);
-    if (tid == 0) *s_flag = handoff_ticket(&a.group_tickets[b * groups + g]) == (unsigned)(members - 1);      // ... before the ticket is taken
+    if (tid == 0) *s_flag = handoff_ticket(&a.group_tickets[b * groups + g]) == (unsigned)(members - 1);
     __syncthreads();
     if (!*s_flag) return false;
     double t = tid < members ? handoff_load(a.slab + (size_t)b * a.G + first + tid) : 0.0;
-    const double group_sum = block_sum<double>(t, s_red);  // a fixed order
+    const double group_sum = block_sum<double, WAVES>(t, s_red);  // a fixed order
     if (tid == 0) {
         handoff_store(a.group_slab + (size_t)b * groups + g, group_sum);
         handoff_store(&a.group_tickets[b * groups + g], 0u);
     }
-    handoff_release();
-    __syncthreads();
-    if (tid == 0) *s_flag = handoff_ticket(&a.tickets[b]) == (unsigned)(groups - 1);
-    __syncthreads();
-    if (!*s_flag) return false;
+    if (!handoff_last([&] { return &a.tickets[b]; }, groups, s_flag)) return false;
     t = 0.0;                                              // a fixed order: thread t takes entries t, t + 256, ...
     for (int e = tid; e < groups; e += THREADS) t += handoff_load(a.group_slab + (size_t)b * groups + e);
-    sum = block_sum<double>(t, s_red);
+    sum = block_sum<double, WAVES>(t, s_red);
     return true;
 }
 

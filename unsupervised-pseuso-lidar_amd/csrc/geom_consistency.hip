@@ -18,7 +18,7 @@
 
 #include "geom_math.h"
 #include "kernel_timer.h"
-#include "mcav_common.h"
+#include "block_ops.h"
 
 namespace mcav {
 
@@ -71,16 +71,6 @@ __device__ __forceinline__ void gc_prepare(const GCArgs& a, int b, int d, gc::Di
     for (int i = 0; i < 9; ++i) { wf.Q[i] = gc_uniform(s_dir->wf.Q[i]); Kinv[i] = gc_uniform(s_dir->Kinv[i]); }
 #pragma unroll
     for (int i = 0; i < 3; ++i) wf.p3[i] = gc_uniform(s_dir->wf.p3[i]);
-}
-
-// sum over the 256 threads in a fixed order; thread 0 gets the total (s: 4 doubles of LDS)
-__device__ __forceinline__ double gc_block_sum(double v, double* s) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((s[0] + s[1]) + s[2]) + s[3];
 }
 
 struct GCTile {
@@ -155,12 +145,8 @@ __global__ __launch_bounds__(GC_THREADS) void geom_consistency_fwd_kernel(GCArgs
         if (k < GC_NRED && part == 0) handoff_store(a.slab + slot * GC_NRED + k, s);
         if (tid == GC_THREADS - 1) handoff_store(a.slab_n + slot, (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]));
     }
-    handoff_release();                                     // the slab stores have been acknowledged ...
-    __syncthreads();
     const int bd = b * 2 + d;
-    if (tid == 0) s_flag = handoff_ticket(&a.tickets[bd]) == (unsigned)(a.G - 1);      // ... before the ticket is taken
-    __syncthreads();
-    if (!s_flag) return;
+    if (!handoff_last([&] { return &a.tickets[bd]; }, a.G, &s_flag)) return;
     // the last workgroup of (sample, direction): its slab entries in a fixed order (8 lanes per value, entries part, part + 8, ...)
     {
         const int k = tid >> 3, part = tid & 7;
@@ -175,14 +161,10 @@ __global__ __launch_bounds__(GC_THREADS) void geom_consistency_fwd_kernel(GCArgs
         if (k >= 1 && k < GC_NRED && part == 0) a.saved[4 + (size_t)bd * 12 + (k - 1)] = s;      // read by the backward: another launch
         unsigned long long n = 0;
         for (int i = tid; i < a.G; i += GC_THREADS) n += handoff_load(a.slab_n + (size_t)bd * a.G + i);
-        const double nn = gc_block_sum((double)n, s_d);    // (integers below 2^53: exact in any order)
+        const double nn = block_sum<double, GC_THREADS / 64>((double)n, s_d);    // (integers below 2^53: exact in any order)
         if (tid == 0) handoff_store(a.dir_n + bd, nn);
     }
-    handoff_release();
-    __syncthreads();
-    if (tid == 0) s_flag = handoff_ticket(&a.tickets[2 * a.B]) == (unsigned)(2 * a.B - 1);
-    __syncthreads();
-    if (!s_flag) return;
+    if (!handoff_last([&] { return &a.tickets[2 * a.B]; }, 2 * a.B, &s_flag)) return;
     // the last (sample, direction): both directions' sums over the samples, in a fixed order
     double ns[2], ss[2];
 #pragma unroll
@@ -192,8 +174,8 @@ __global__ __launch_bounds__(GC_THREADS) void geom_consistency_fwd_kernel(GCArgs
             n += handoff_load(a.dir_n + i * 2 + dd);
             s += handoff_load(a.dir_s + i * 2 + dd);
         }
-        ns[dd] = gc_block_sum(n, s_d);
-        ss[dd] = gc_block_sum(s, s_d);
+        ns[dd] = block_sum<double, GC_THREADS / 64>(n, s_d);
+        ss[dd] = block_sum<double, GC_THREADS / 64>(s, s_d);
     }
     if (tid == 0) {
         a.saved[0] = ns[0]; a.saved[1] = ns[1]; a.saved[2] = ss[0]; a.saved[3] = ss[1];

@@ -11,7 +11,7 @@
 //            keys, three passes over the stored keys with the histograms in LDS (eval_depth.hip's scheme, its global histogram and its
 //            extra launches left out: nothing crosses a workgroup, so no hand-off and no zero-filled state); thread 0 writes the row.
 // LDS integer atomics only (counts: exact in any order): rows and mask are bit-identical from run to run.
-#include "mcav_common.h"
+#include "block_ops.h"
 #include "ground_math.h"
 
 namespace mcav {
@@ -19,9 +19,7 @@ namespace gs {
 
 constexpr int TILE_H = 8, TILE_W = 32, THREADS = TILE_H * TILE_W;
 constexpr int HALO_H = TILE_H + 2, HALO_W = TILE_W + 2;
-constexpr int SEL_THREADS = 1024, BINS = 2048, PASSES = 3;
-__constant__ const int sel_shift[PASSES] = {21, 10, 0};
-__constant__ const int sel_width[PASSES] = {11, 11, 10};
+constexpr int SEL_THREADS = 1024, SEL_WAVES = SEL_THREADS / 64, BINS = RADIX_BINS;
 
 struct Args {
     const float* m;                      // [B, h, w]
@@ -106,17 +104,16 @@ __device__ __forceinline__ void hist_add(unsigned* bins, bool take, unsigned d) 
 
 __global__ __launch_bounds__(SEL_THREADS) void gs_select_kernel(Args a) {
     __shared__ unsigned lh[2][BINS];
-    __shared__ unsigned wtot[SEL_THREADS / 64];
-    __shared__ unsigned s_pre[2], s_left[2], s_count;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ unsigned wtot[SEL_WAVES];
+    __shared__ unsigned s_pre[2], s_left[2];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    unsigned count = 0;                                    // the number of ground pixels, in every thread
     const unsigned n = (unsigned)(a.h - 2) * (unsigned)(a.w - 2);
     const unsigned* kb = a.keys + (size_t)b * n;
-    for (int p = 0; p < PASSES; ++p) {
+    for (int p = 0; p < RADIX_PASSES; ++p) {
         for (int i = tid; i < 2 * BINS; i += SEL_THREADS) (&lh[0][0])[i] = 0u;
         __syncthreads();                                   // (also: every thread has read the previous pass's state)
-        const int shift = sel_shift[p], top = shift + sel_width[p];
-        const unsigned dmask = (1u << sel_width[p]) - 1u;
-        const unsigned pmask = top >= 32 ? 0u : ~0u << top;
+        const auto [shift, dmask, pmask] = radix_pass(p);
         const unsigned pre0 = p ? s_pre[0] & pmask : 0u, pre1 = p ? s_pre[1] & pmask : 0u;
         const bool two = p && pre0 != pre1;                // neighbouring ranks nearly always share their prefix: one histogram serves both
         for (unsigned base = 0; base < n; base += SEL_THREADS) {      // uniform over the workgroup
@@ -128,44 +125,17 @@ __global__ __launch_bounds__(SEL_THREADS) void gs_select_kernel(Args a) {
             if (two) hist_add(lh[1], gnd && (key & pmask) == pre1, d);      // (uniform; pass 0: every key matches both ranks)
         }
         __syncthreads();
-        if (p == 0) {                                      // the number of ground pixels: the sum of every bin
-            unsigned s = lh[0][2 * tid] + lh[0][2 * tid + 1];
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
-            if (lane == 0) wtot[wave] = s;
-            __syncthreads();
-            if (tid == 0) {
-                unsigned tot = 0;
-                for (int w = 0; w < SEL_THREADS / 64; ++w) tot += wtot[w];
-                s_count = tot;
-            }
-            __syncthreads();
-            if (s_count == 0) break;                       // uniform
+        if (p == 0) {                                      // the sum of every bin
+            count = block_sum<unsigned, SEL_WAVES>(lh[0][2 * tid] + lh[0][2 * tid + 1], wtot);
+            if (count == 0) break;                         // uniform
         }
-        const unsigned count = s_count;
         unsigned pick[2] = {0u, 0u}, left[2] = {0u, 0u};
-        bool mine[2] = {false, false};
+        bool mine[2];
         for (int r = 0; r < 2; ++r) {
             const unsigned* src = lh[two ? r : 0];
-            const unsigned c0 = src[2 * tid], c1 = src[2 * tid + 1], s = c0 + c1;
-            unsigned v = s;                                // inclusive scan over the wave, then over the sixteen waves
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const unsigned t = __shfl_up(v, off, 64);
-                if (lane >= off) v += t;
-            }
-            __syncthreads();
-            if (lane == 63) wtot[wave] = v;
-            __syncthreads();
-            unsigned excl = v - s;
-            for (int w = 0; w < wave; ++w) excl += wtot[w];
+            const unsigned c[2] = {src[2 * tid], src[2 * tid + 1]};
             const unsigned k = p ? s_left[r] : (r == 0 ? (count - 1) / 2 : count / 2);
-            if (k >= excl && k < excl + s) {
-                const bool second = k >= excl + c0;
-                mine[r] = true;
-                pick[r] = (unsigned)(2 * tid + (second ? 1 : 0));
-                left[r] = k - excl - (second ? c0 : 0u);
-            }
+            mine[r] = pick_bin<2, SEL_WAVES>(c, k, wtot, pick[r], left[r]);
         }
         __syncthreads();                                   // every thread has read the state
         for (int r = 0; r < 2; ++r)
@@ -177,7 +147,6 @@ __global__ __launch_bounds__(SEL_THREADS) void gs_select_kernel(Args a) {
     }
     if (tid == 0) {
         float row[4];
-        const unsigned count = s_count;
         image_row(count, count ? ev::bits_float(s_pre[0]) : 0.0f, count ? ev::bits_float(s_pre[1]) : 0.0f, a.camera_height, a.min_ground,
                   a.fallback, row);
         for (int k = 0; k < 4; ++k) a.rows[4 * b + k] = row[k];

@@ -32,25 +32,21 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 #define MCAV_KNOB_FLOAT(name, dflt) (dflt)
 #endif
 
-// Sum over the 64 lanes of a wavefront; every lane gets the total.
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------- cross-workgroup hand-off inside ONE launch
 // "Every workgroup leaves a partial result; the last one to arrive (a ticket) finishes the job."  What a workgroup writes for ANOTHER to
 // read inside the same launch must pass the XCD-local L2: on gfx950 each of the 8 XCDs has its own L2 and only accesses at agent scope (the
 // instruction's sc1 bit) go through to / come from the coherence point.  The protocol, every step explicit in the ISA (tests/test_isa_handoff.py
 // checks the compiled kernels for it on the CPU, so a compiler or ROCm upgrade that changes the code generation is caught):
 //   producer:  handoff_store (global_store ... sc1) of every word it publishes
+//              handoff_last(ticket, members, s_flag), called by every thread of the workgroup (ticket: a callable that returns the ticket's
+//              address, so that only the drawing thread forms it), does the rest in the one order that works:
 //              handoff_release(): s_waitcnt vmcnt(0) -- EVERY thread waits until its own stores are acknowledged (a workgroup-scope release
 //              fence does NOT do that: the compiler is entitled to -- and round 3's build did -- issue the ticket while the stores were still in
 //              flight to another L2 channel; the hand-off then worked by timing only.  ADVICE round 3.)
 //              __syncthreads(), then ONE thread takes the ticket: an agent-scope atomic add (performed at the coherence point)
-//   finisher:  the thread that drew the last ticket tells its workgroup through LDS + __syncthreads(); the loads that follow are issued after
-//              the ticket's value has returned (in-order issue behind the s_waitcnt on the atomic's result) and are handoff_load (sc1).
+//   finisher:  the workgroup to which handoff_last returns true: the thread that drew the last of the `members` tickets has told the others
+//              through LDS + __syncthreads().  The loads that follow are issued after the ticket's value has returned (in-order issue behind
+//              the s_waitcnt on the atomic's result) and are handoff_load (sc1).
 // An agent-scope release / acquire FENCE pair would be the portable spelling; on this chip it is a write-back + invalidate of the whole
 // XCD L2 per workgroup, which took the loss kernel's gather lines with it and doubled its time.
 __device__ __forceinline__ void handoff_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -64,5 +60,14 @@ __device__ __forceinline__ void handoff_release() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // ... and this thread's global stores have been acknowledged
 }
 __device__ __forceinline__ unsigned handoff_ticket(unsigned* t) { return __hip_atomic_fetch_add(t, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+// ticket(): the address of the ticket that the `members` workgroups share; only the drawing thread calls it (s_flag: one int of LDS)
+template <class Ticket>
+__device__ __forceinline__ bool handoff_last(Ticket ticket, int members, int* s_flag) {
+    handoff_release();                                           // this thread's published words have been acknowledged ...
+    __syncthreads();
+    if (threadIdx.x == 0) *s_flag = handoff_ticket(ticket()) == (unsigned)(members - 1);      // ... before the workgroup's ticket is taken
+    __syncthreads();
+    return *s_flag != 0;
+}
 
 }  // namespace mcav

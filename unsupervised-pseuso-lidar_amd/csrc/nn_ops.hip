@@ -130,11 +130,7 @@ __global__ __launch_bounds__(256) void bn_partial_finalize_kernel(const float* s
         handoff_store(o + c, a);
         handoff_store(o + C + c, b);
     }
-    handoff_release();
-    __syncthreads();
-    if (threadIdx.x == 0) s_last = handoff_ticket(&tickets[blockIdx.x]) == (unsigned)(nsl * groups - 1);
-    __syncthreads();
-    if (!s_last) return;
+    if (!handoff_last([&] { return &tickets[blockIdx.x]; }, nsl * groups, &s_last)) return;
     for (int gg = 0; gg < groups; ++gg) {
         a = 0.0; b = 0.0;
         if (c < C) {

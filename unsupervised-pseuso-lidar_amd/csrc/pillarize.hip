@@ -11,7 +11,7 @@
 // Integer atomics only, nothing returns to the host, no allocation: the call can be captured, and two runs give the same bytes.
 #include <limits.h>
 
-#include "mcav_common.h"
+#include "block_ops.h"
 #include "pillar_math.h"
 
 namespace mcav {
@@ -25,34 +25,12 @@ constexpr int GATHER_BLOCKS = 8192;              // 32 single-wave blocks per CU
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-struct Pair {
-    unsigned points, pillars;
-};
-__device__ __forceinline__ Pair operator+(Pair a, Pair b) { return Pair{a.points + b.points, a.pillars + b.pillars}; }
-
-// Exclusive scan of one Pair per thread over a block of WAVES wavefronts; total: the block's sum, in every thread.
-template <int WAVES>
-__device__ __forceinline__ Pair block_scan(Pair v, Pair* wsum, Pair& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    Pair inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const unsigned a = __shfl_up(inc.points, off, 64), b = __shfl_up(inc.pillars, off, 64);
-        if (lane >= off) { inc.points += a; inc.pillars += b; }
-    }
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    Pair before{0u, 0u};
-    total = Pair{0u, 0u};
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const Pair s = wsum[w];
-        if (w < wave) before = before + s;
-        total = total + s;
-    }
-    __syncthreads();                                       // wsum is free again
-    return Pair{before.points + inc.points - v.points, before.pillars + inc.pillars - v.pillars};
-}
+// The scans carry two counters at once, points in the low word of a Pair and pillars (non-empty cells) in the high word: both totals are
+// below 2^31 (the caller's checks), so nothing carries from one into the other.
+typedef unsigned long long Pair;
+__device__ __forceinline__ Pair pair_of(unsigned points, unsigned pillars) { return (Pair)points | (Pair)pillars << 32; }
+__device__ __forceinline__ unsigned points_of(Pair p) { return (unsigned)p; }
+__device__ __forceinline__ unsigned pillars_of(Pair p) { return (unsigned)(p >> 32); }
 
 // the four counters of a thread; beyond the grid they read as empty cells
 __device__ __forceinline__ void load_cells(const unsigned* cells, unsigned M, unsigned j, unsigned (&c)[PER_THREAD]) {
@@ -63,6 +41,13 @@ __device__ __forceinline__ void load_cells(const unsigned* cells, unsigned M, un
 #pragma unroll
         for (int e = 0; e < PER_THREAD; ++e) c[e] = j + e < M ? cells[j + e] : 0u;
     }
+}
+
+__device__ __forceinline__ Pair cells_sum(const unsigned (&c)[PER_THREAD]) {
+    Pair v = 0;
+#pragma unroll
+    for (int e = 0; e < PER_THREAD; ++e) v += pair_of(c[e], c[e] ? 1u : 0u);
+    return v;
 }
 
 __device__ __forceinline__ int live_points(const int* offsets, int B, int n_max) { return min(offsets[B], n_max); }
@@ -86,27 +71,17 @@ __global__ __launch_bounds__(THREADS) void pil_reduce_kernel(const unsigned* cel
     __shared__ Pair wsum[THREADS / 64];
     unsigned c[PER_THREAD];
     load_cells(cells, M, blockIdx.x * (unsigned)TILE + threadIdx.x * PER_THREAD, c);
-    Pair v{0u, 0u}, total;
-#pragma unroll
-    for (int e = 0; e < PER_THREAD; ++e) { v.points += c[e]; v.pillars += c[e] ? 1u : 0u; }
-    block_scan<THREADS / 64>(v, wsum, total);
-    if (threadIdx.x == 0) { tile_points[blockIdx.x] = total.points; tile_pillars[blockIdx.x] = total.pillars; }
+    const Pair total = block_sum<Pair, THREADS / 64>(cells_sum(c), wsum);
+    if (threadIdx.x == 0) { tile_points[blockIdx.x] = points_of(total); tile_pillars[blockIdx.x] = pillars_of(total); }
 }
 
 // exclusive scan of the tiles' sums in one block, 1024 per pass; the totals go to cells[M] (the end of the last segment) and pillar_offsets[B]
 __global__ __launch_bounds__(1024) void pil_scan_kernel(unsigned* tile_points, unsigned* tile_pillars, unsigned ntiles, unsigned* cells, unsigned M,
                                                         int* pillar_offsets, int B) {
     __shared__ Pair wsum[16];
-    Pair carry{0u, 0u};
-    for (unsigned base = 0; base < ntiles; base += 1024u) {
-        const unsigned i = base + threadIdx.x;
-        const Pair v = i < ntiles ? Pair{tile_points[i], tile_pillars[i]} : Pair{0u, 0u};
-        Pair total;
-        const Pair ex = block_scan<16>(v, wsum, total);
-        if (i < ntiles) { tile_points[i] = carry.points + ex.points; tile_pillars[i] = carry.pillars + ex.pillars; }
-        carry = carry + total;
-    }
-    if (threadIdx.x == 0) { cells[M] = carry.points; pillar_offsets[B] = (int)carry.pillars; }
+    const Pair total = chunked_scan<Pair, 16>((int)ntiles, wsum, [&](int i) { return pair_of(tile_points[i], tile_pillars[i]); },
+                                              [&](int i, Pair v) { tile_points[i] = points_of(v); tile_pillars[i] = pillars_of(v); });
+    if (threadIdx.x == 0) { cells[M] = points_of(total); pillar_offsets[B] = (int)pillars_of(total); }
 }
 
 // counters -> segment starts (in place: a thread rewrites the four it read); the rank and the cell of every pillar; pillar_offsets[b] at
@@ -117,11 +92,9 @@ __global__ __launch_bounds__(THREADS) void pil_apply_kernel(unsigned* cells, uns
     const unsigned j = blockIdx.x * (unsigned)TILE + threadIdx.x * PER_THREAD;
     unsigned c[PER_THREAD];
     load_cells(cells, M, j, c);
-    Pair v{0u, 0u}, total;
-#pragma unroll
-    for (int e = 0; e < PER_THREAD; ++e) { v.points += c[e]; v.pillars += c[e] ? 1u : 0u; }
-    const Pair ex = block_scan<THREADS / 64>(v, wsum, total);
-    unsigned start = tile_points[blockIdx.x] + ex.points, rank = tile_pillars[blockIdx.x] + ex.pillars;
+    Pair total;
+    const Pair ex = block_scan<Pair, THREADS / 64>(cells_sum(c), wsum, total);
+    unsigned start = tile_points[blockIdx.x] + points_of(ex), rank = tile_pillars[blockIdx.x] + pillars_of(ex);
     unsigned s[PER_THREAD];
 #pragma unroll
     for (int e = 0; e < PER_THREAD; ++e) {

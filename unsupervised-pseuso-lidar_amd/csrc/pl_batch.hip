@@ -6,7 +6,7 @@
 //           same count / scan / scatter over the cells
 // Every pass recomputes the point instead of storing it (4 B read per network pixel, 16 B written per point); nothing returns to the host,
 // no copy from the host and no allocation: the call can be captured.  No float atomics: bit-identical from run to run.
-#include "mcav_common.h"
+#include "block_ops.h"
 #include "pl_math.h"
 
 namespace mcav {
@@ -73,23 +73,6 @@ __device__ __forceinline__ float pixel_intensity(const Args& a, int b, int r, in
     return sample(a.intensity + (size_t)b * a.h * a.w, a.h, a.w, Hb, Wb, r, c);
 }
 
-// flags of one block -> its count (count pass) or each flagged thread's rank within the block (scatter pass)
-__device__ __forceinline__ unsigned block_count(bool v, unsigned* wsum) {
-    const unsigned long long m = __ballot(v);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (unsigned)__popcll(m);
-    __syncthreads();
-    return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-__device__ __forceinline__ unsigned block_rank(bool v, unsigned* wsum) {
-    const unsigned long long m = __ballot(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wsum[wave] = (unsigned)__popcll(m);
-    __syncthreads();
-    unsigned before = 0;
-    for (int w = 0; w < wave; ++w) before += wsum[w];
-    return before + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-}
-
 __global__ __launch_bounds__(THREADS) void plb_count_kernel(Args a, unsigned* counts) {
     __shared__ unsigned wsum[THREADS / 64];
     const int b = blockIdx.x / a.per_image;
@@ -97,35 +80,18 @@ __global__ __launch_bounds__(THREADS) void plb_count_kernel(Args a, unsigned* co
     float d;
     double q[3];
     int r, c;
-    const unsigned n = block_count(pixel_survives(a, b, p, d, q, r, c), wsum);
+    const unsigned n = block_count<THREADS / 64>(pixel_survives(a, b, p, d, q, r, c), wsum);
     if (threadIdx.x == 0) counts[blockIdx.x] = n;
 }
 
 // Exclusive scan of the per-block counts in one block (1024 entries per pass), total -> counts[nblocks]; then the images' slices:
 // offsets[b] = rows before image b, an image of n survivors owning ceil(n / step) rows.
 __global__ __launch_bounds__(1024) void plb_scan_kernel(unsigned* counts, int nblocks, int per_image, int B, unsigned step, int* offsets) {
-    __shared__ unsigned sh[1024];
-    __shared__ unsigned carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nblocks; base += 1024) {
-        const int i = base + threadIdx.x;
-        const unsigned v = i < nblocks ? counts[i] : 0u;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const unsigned t = (int)threadIdx.x >= off ? sh[threadIdx.x - off] : 0u;
-            __syncthreads();
-            sh[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < nblocks) counts[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
+    __shared__ unsigned wsum[16];
+    const unsigned total = chunked_scan<unsigned, 16>(nblocks, wsum, [&](int i) { return counts[i]; }, [&](int i, unsigned v) { counts[i] = v; });
+    __syncthreads();                                   // thread 0 reads what the others stored
     if (threadIdx.x == 0) {
-        counts[nblocks] = carry;
+        counts[nblocks] = total;
         unsigned rows = 0;
         for (int b = 0; b < B; ++b) {
             offsets[b] = (int)rows;
@@ -145,7 +111,7 @@ __global__ __launch_bounds__(THREADS) void plb_scatter_kernel(Args a, const unsi
     double q[3];
     int r, c;
     const bool v = pixel_survives(a, b, p, d, q, r, c);
-    const unsigned k = (scan[blockIdx.x] - scan[(size_t)b * a.per_image]) + block_rank(v, wsum);       // rank among the image's survivors
+    const unsigned k = (scan[blockIdx.x] - scan[(size_t)b * a.per_image]) + block_rank<THREADS / 64>(v, wsum);       // rank among the image's survivors
     if (v && k % step == 0) {
         const size_t o = (size_t)offsets[b] + k / step;
         if (o < capacity) {
@@ -181,7 +147,7 @@ __global__ __launch_bounds__(THREADS) void plb_cell_count_kernel(Args a, const u
     __shared__ unsigned wsum[THREADS / 64];
     int b;
     unsigned long long word;
-    const unsigned n = block_count(cell_filled(a, cells, per_cells, b, word), wsum);
+    const unsigned n = block_count<THREADS / 64>(cell_filled(a, cells, per_cells, b, word), wsum);
     if (threadIdx.x == 0) counts[blockIdx.x] = n;
 }
 
@@ -191,7 +157,7 @@ __global__ __launch_bounds__(THREADS) void plb_cell_scatter_kernel(Args a, const
     int b;
     unsigned long long word = EMPTY_CELL;
     const bool v = cell_filled(a, cells, per_cells, b, word);
-    const size_t o = (size_t)scan[blockIdx.x] + block_rank(v, wsum);
+    const size_t o = (size_t)scan[blockIdx.x] + block_rank<THREADS / 64>(v, wsum);
     if (v && o < capacity) {
         float d;
         double q[3];

@@ -4,7 +4,7 @@
 //                            the velodyne frame, x >= 0 & z < 1 m filter, every sparsity-th survivor: an ORDER-PRESERVING
 //                            stream compaction (count -> scan -> scatter), float64 like the reference's numpy arithmetic.
 // Reductions are two-stage with a fixed order (bit-reproducible); no float atomics.
-#include "mcav_common.h"
+#include "block_ops.h"
 
 namespace mcav {
 
@@ -128,27 +128,9 @@ __global__ __launch_bounds__(PL_THREADS) void pl_count_kernel(const float* depth
 
 // exclusive scan of the per-block counts, one block (the image has at most a few thousand blocks); total -> counts[nblocks]
 __global__ __launch_bounds__(1024) void pl_scan_kernel(unsigned* counts, int nblocks) {
-    __shared__ unsigned sh[1024];
-    __shared__ unsigned carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (int base = 0; base < nblocks; base += 1024) {
-        const int i = base + threadIdx.x;
-        const unsigned v = i < nblocks ? counts[i] : 0u;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int off = 1; off < 1024; off <<= 1) {
-            const unsigned t = (int)threadIdx.x >= off ? sh[threadIdx.x - off] : 0u;
-            __syncthreads();
-            sh[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < nblocks) counts[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry += sh[1023];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) counts[nblocks] = carry;
+    __shared__ unsigned wsum[16];
+    const unsigned total = chunked_scan<unsigned, 16>(nblocks, wsum, [&](int i) { return counts[i]; }, [&](int i, unsigned v) { counts[i] = v; });
+    if (threadIdx.x == 0) counts[nblocks] = total;
 }
 
 __global__ __launch_bounds__(PL_THREADS) void pl_scatter_kernel(const float* depth, int cols, size_t n, PLCalib c, const unsigned* offsets,

@@ -12,7 +12,7 @@
 #include <type_traits>
 #include <vector>
 
-#include "mcav_common.h"
+#include "block_ops.h"
 #include "kernel_timer.h"
 #include "warp_math.h"
 
@@ -261,8 +261,6 @@ __device__ __forceinline__ WarpFast uniform_warp(const WarpFast& w) {
 // mcav_common.h: agent-scope (sc1) stores, an explicit s_waitcnt vmcnt(0) in every thread before the ticket, sc1 loads in the finisher.  The
 // first version used __threadfence(), i.e. a write-back and invalidate of the XCD's whole L2 per workgroup: 660 (L1) / 3840 (SSIM) of those per
 // launch took the gathers' cached lines with them and doubled the kernels' time.
-__device__ __forceinline__ void slab_store(float* p, float v) { handoff_store(p, v); }
-__device__ __forceinline__ void order_before_ticket() { handoff_release(); }
 
 constexpr int RED_LD = 256 + 8;      // one pad float per 32 threads: the transposed reads are conflict-free
 
@@ -283,17 +281,13 @@ __device__ __forceinline__ void block_sum_to_slab(const float* acc, float (*sred
     s += __shfl_xor(s, 1, 64);
     s += __shfl_xor(s, 2, 64);
     s += __shfl_xor(s, 4, 64);
-    if (k < N && part == 0) slab_store(out + slot(k), s);
+    if (k < N && part == 0) handoff_store(out + slot(k), s);
 }
 
 // after the workgroup's slab entry is written: ticket, and the last workgroup of the sample finishes the sample
 __device__ __forceinline__ void block_finish(const WLArgs& a, int b, int nblk, double (*s64)[SLAB], int* s_flag) {
     const int tid = threadIdx.x;
-    order_before_ticket();                                       // this workgroup's (agent-scope) slab stores have completed ...
-    __syncthreads();
-    if (tid == 0) *s_flag = handoff_ticket(&a.tickets[b]) == (unsigned)(nblk - 1);      // ... before its ticket is taken
-    __syncthreads();
-    if (!*s_flag) return;
+    if (!handoff_last([&] { return &a.tickets[b]; }, nblk, s_flag)) return;
     const float* slab = a.slab + (size_t)b * nblk * SLAB;
     constexpr int PARTS = 256 / SLAB;                            // 6 x 40 = 240 threads
     if (tid < PARTS * SLAB) {
@@ -329,7 +323,7 @@ __device__ __forceinline__ void block_finish(const WLArgs& a, int b, int nblk, d
         handoff_store(a.sample_loss + b * 2 + 0, s64[0][0]);
         handoff_store(a.sample_loss + b * 2 + 1, s64[0][1]);
         handoff_store(&a.tickets[b], 0u);
-        order_before_ticket();
+        handoff_release();
         if (handoff_ticket(&a.tickets[a.B]) == (unsigned)(a.B - 1)) {
             double l0 = 0.0, l1 = 0.0;
             for (int i = 0; i < a.B; ++i) {

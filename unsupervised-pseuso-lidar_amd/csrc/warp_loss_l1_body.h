@@ -276,7 +276,7 @@
         }
         __syncthreads();                                         // (sD and sred do not alias, but every wavefront must be out of the loop's barriers)
         block_sum_to_slab<RED_N0>(acc, sred, slab, [](int k) { return k; });
-        if (tid >= RED_N0 && tid < SLAB) slab_store(slab + tid, 0.f);      // warp 2's slots
+        if (tid >= RED_N0 && tid < SLAB) handoff_store(slab + tid, 0.f);      // warp 2's slots
     } else {
         // ---- pass 1: warp 2 (tgt sampled with depth(ref0) and the inverted pose[0], compared with ref1: losses.py:203-207); d loss / d disp(ref0)
         const float gw2 = g0 * a.tw[2] * invN, lw2 = a.tw[2] * invN;
@@ -373,7 +373,7 @@
         }
         __syncthreads();                                         // (the stage and sred alias)
         block_sum_to_slab<RED_N1>(acc, sred, slab, [](int k) { return k == 0 ? 0 : 25 + k; });      // loss share; dP of warp 2 -> slots 26..37
-        if (tid >= 1 && tid < 26) slab_store(slab + tid, 0.f);
-        if (tid >= 38 && tid < SLAB) slab_store(slab + tid, 0.f);
+        if (tid >= 1 && tid < 26) handoff_store(slab + tid, 0.f);
+        if (tid >= 38 && tid < SLAB) handoff_store(slab + tid, 0.f);
     }
     block_finish(a, b, a.G0 + a.G1, reinterpret_cast<double (*)[SLAB]>(&sred[0][0]), &s_flag);

@@ -473,5 +473,5 @@
     float* const slab = a.slab + ((size_t)b * nblk + blk) * SLAB;
     __syncthreads();                                   // every reader of the constants (and of sC) is done: their LDS is re-used below
     block_reduce_store<NACC, true>(acc, slab, sred);
-    if (threadIdx.x >= NACC && threadIdx.x < SLAB) slab_store(slab + threadIdx.x, 0.f);
+    if (threadIdx.x >= NACC && threadIdx.x < SLAB) handoff_store(slab + threadIdx.x, 0.f);
     block_finish(a, b, nblk, s64, &s_flag);
