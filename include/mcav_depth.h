@@ -433,6 +433,37 @@ int mcav_pillarize(const float* points, const int* offsets, int B, long long n_m
                    float vy, int nx, int ny, int max_points, int flags, float* voxels, int* coords, int* num_points, long long capacity,
                    int* pillar_offsets, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Pillars -> pillar features -> bird's-eye-view pseudo-image, the first layers of a LiDAR 3-D detector (PointPillars / SECOND / OpenPCDet:
+ * PillarVFE's Linear + BatchNorm1d + ReLU + max over the pillar's points with the BatchNorm folded into the layer, then
+ * PointPillarScatter), in one launch.  The definition is tests/pfn_ref.py; the arithmetic is csrc/pfn_math.h.
+ *   input    voxels [capacity, max_points, columns] float32, coords [capacity, 4] int32 = (b, 0, iy, ix), num_points [capacity] int32 and
+ *            pillar_offsets int32 [B + 1] on the device, as mcav_pillarize leaves them: rows in ascending (b, iy, ix) order, image b owns
+ *            rows pillar_offsets[b] .. pillar_offsets[b + 1]; P = min(pillar_offsets[B], capacity) and rows at and beyond P are never read.
+ *   layer    weight [c_out, columns], bias [c_out], bias_pad [c_out] float32 on the device; c_out a multiple of 32 in 32..128
+ *   pre      for pillar p, slot k, channel o: acc = bias[o], then acc = fmaf(voxels[p, k, c], weight[o, c], acc) for c = 0 .. columns - 1
+ *            in ascending order: float32, one rounding per column
+ *   act      acc > 0 ? acc : (acc != acc ? acc : +0.0f): a NaN stays a NaN; -0.0, negative values and -inf give +0.0
+ *   feat     feat[p, o] = the NaN-propagating maximum (torch.max, not fmaxf) of act over the slots k < n, n = num_points[p] clamped to
+ *            [0, max_points]; if n < max_points, act(bias_pad[o]) joins the maximum: what second.pytorch and OpenPCDet compute, which put
+ *            the zero-masked padding rows through the layer, when bias_pad = bias; any bias_pad <= 0 ignores the padding.  Which NaN comes
+ *            out is not defined.
+ *   canvas   device [B, c_out, ny, nx] float32 (MCAV_PFN_NHWC: [B, ny, nx, c_out]): canvas[b, o, iy, ix] = feat[p, o] for the row p with
+ *            coords[p] = (b, *, iy, ix), +0.0 in every other element.  One call writes every element: no zero-fill by the caller.
+ *   features device [capacity, c_out] float32 or NULL: feat in the rows below P; rows at and beyond P are not written.
+ * A row whose (b, iy, ix) lies outside the canvas is skipped (with a canvas its features row is not written either); rows that are not in
+ * ascending order give an unspecified canvas; neither reads or writes outside the buffers.  canvas may be NULL when features is not: the
+ * features alone, for every row below P whatever its coords hold (nx and ny are still checked).
+ * No atomics, no workspace, no host synchronisation, allocation or copy: the call can be captured, and two runs give the same bytes.
+ * 1 launch.  A canvas whose address is a multiple of 16 (and, for [B, c_out, ny, nx], nx a multiple of 4) goes out in 16-byte stores.
+ * Returns MCAV_E_INVALID for a null voxels, coords, num_points, pillar_offsets, weight, bias or bias_pad, canvas and features both null,
+ * an address that is no multiple of 4, B <= 0, B > 65535, capacity < 0, nx or ny < 1, B * ny * nx >= 2^31, max_points outside [1, 64],
+ * columns outside {4, 9}, c_out outside {32, 64, 96, 128} or unknown flag bits; nothing is launched then. */
+#define MCAV_PFN_NHWC 1      /* canvas [B, ny, nx, C_out] instead of [B, C_out, ny, nx] */
+int mcav_pillar_pseudo_image(const float* voxels, const int* coords, const int* num_points, const int* pillar_offsets,
+                             int B, long long capacity, int max_points, int columns, int nx, int ny,
+                             const float* weight, const float* bias, const float* bias_pad, int c_out, int flags,
+                             float* canvas, float* features /* may be null */, void* stream);
+
 /* Graph-based depth correction from sparse LiDAR (GDC): You et al., "Pseudo-LiDAR++: Accurate Depth for 3D Object Detection in Autonomous
  * Driving", ICLR 2020, section 4; the reference's notes pseudo-lidar/PL_development/research/pseudo_lidar++.md: "create a KNN graph; use
  * sparse LiDAR point clouds to bias and correct depth".  A predicted depth map has the right local shape and a smooth error; a few exact

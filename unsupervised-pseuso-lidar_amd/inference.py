@@ -4,11 +4,13 @@
     disp = inf.disparity(images)                       # [B, 1, h, w], evaluation mode, no gradients
     cb = inf.clouds(samples, beams=beam_tables())      # a pseudo_lidar.CloudBatch for one loader batch
     pb = inf.pillars(samples, max_points=32)           # a pseudo_lidar.PillarBatch: what a LiDAR 3-D detector reads
+    img = inf.pseudo_images(samples, pfn)              # [B, C_out, ny, nx]: what the detector's convolutional backbone reads
     n = inf.export("out")                              # out/<date>/<drive>/pseudo_velodyne/data/<frame>.bin for every frame of the split
 
     python inference.py --config C --checkpoint X --out DIR [--beams NB NA] [--scale S | --scale ground] [--max-depth D]
                         [--camera-height M] [--ground-angle DEG] [--ground-min N]
-                        [--pillars [--pillar-size VX VY] [--pillar-points N] [--pillar-range X0 X1 Y0 Y1 Z0 Z1]]
+                        [--pillars [--pillar-size VX VY] [--pillar-points N] [--pillar-range X0 X1 Y0 Y1 Z0 Z1]
+                         [--pfn CHECKPOINT [--pfn-prefix P]]]
                         [--gdc [--gdc-beams 5 7 9 11] [--gdc-iters 400] [--gdc-k 10] [--gdc-radius 3]]
 
 --gdc corrects every frame's depth map against a few beams of its own Velodyne scan before the cloud is made (Pseudo-LiDAR++'s
@@ -17,6 +19,9 @@ scan thinned to --gdc-beams of its 64 -> project_batch(input="depth").  It needs
 
 --pillars also writes out/<date>/<drive>/pseudo_pillars/data/<frame>.npz (voxels [P, N, 4], coords [P, 4] = (image in its batch, 0, iy,
 ix), num_points [P]) beside every .bin: the cloud voxelised on the GPU (pseudo_lidar.pillarize; default PointPillars' KITTI grid).
+--pfn CHECKPOINT reads a detector's pillar feature net from it (pseudo_lidar.PillarFeatureNet.from_state_dict: `linear.weight` and the
+BatchNorm `norm.*` under --pfn-prefix, 4 input columns; the state dict itself or under `model_state` / `state_dict`) and adds features
+[P, C_out] to every .npz; the dense pseudo-image (55 MB a frame) is not written.
 
 --scale ground gives every frame its own metric scale from its ground plane (pseudo_lidar.ground_scale: no ground truth, no stereo); a
 frame without enough ground pixels gets an empty cloud.
@@ -33,7 +38,7 @@ import numpy as np
 import torch
 import yaml
 
-from pseudo_lidar import PillarGrid, PseudoLiDAR, beam_tables, gdc as gdc_correct, ground_scale
+from pseudo_lidar import PillarFeatureNet, PillarGrid, PseudoLiDAR, beam_tables, gdc as gdc_correct, ground_scale
 
 
 class Inference:
@@ -129,6 +134,12 @@ class Inference:
         pb.cloud = cloud
         return pb
 
+    @torch.no_grad()
+    def pseudo_images(self, samples, pfn, layout="nchw", **pillar_kw):
+        """One batch of a datasets.calibration loader -> [B, C_out, ny, nx]: pillars(samples, **pillar_kw) through the PillarFeatureNet
+        `pfn` into the bird's-eye-view pseudo-image (pseudo_lidar.PillarFeatureNet.pseudo_image).  Nothing is read back."""
+        return pfn.pseudo_image(self.pillars(samples, **pillar_kw), layout=layout)
+
     def loader(self):
         """Every frame of the split, in order, with its calibration"""
         from dataloaders import PrefetchLoader, UnSupKittiDataset, raw_collate
@@ -160,10 +171,13 @@ class Inference:
         """<out_dir>/<date>/<drive>/pseudo_pillars/data/<frame>.npz of .../<date>/<drive>/image_02/data/<frame>.png"""
         return Inference._frame_path(out_dir, image_path, "pseudo_pillars", ".npz")
 
-    def export(self, out_dir, loader=None, pillars=None, **kw):
+    def export(self, out_dir, loader=None, pillars=None, pfn=None, **kw):
         """Writes one KITTI .bin (float32 x y z i) per frame of the split and returns the number of frames.  pillars: None, or a dict of
         pillarize's keywords (grid, max_points, decorate; {} for the defaults): every frame's .npz of voxels, coords and num_points is
-        written too, at the cost of one more read-back of offsets and one of the used rows per batch."""
+        written too, at the cost of one more read-back of offsets and one of the used rows per batch.  pfn: a PillarFeatureNet whose
+        features [P, C_out] of every frame's pillars go into the .npz as well (needs pillars)."""
+        if pfn is not None and pillars is None:
+            raise ValueError("Inference.export: pfn needs pillars")
         n = 0
         for samples in (self.loader() if loader is None else loader):
             paths = [self.cloud_path(out_dir, p) for p in samples['path']]
@@ -175,7 +189,11 @@ class Inference:
                 npz = [self.pillar_path(out_dir, p) for p in samples['path']]
                 for p in npz:
                     os.makedirs(os.path.dirname(p), exist_ok=True)
-                cloud.pillars(**pillars).save_npz(npz)
+                pb = cloud.pillars(**pillars)
+                if pfn is None:
+                    pb.save_npz(npz)
+                else:
+                    pb.save_npz(npz, features=pfn.features(pb))
             n += len(paths)
         return n
 
@@ -191,6 +209,24 @@ def pillar_arguments(args):
         return None
     r = args.pillar_range
     return dict(grid=PillarGrid(x=(r[0], r[1]), y=(r[2], r[3]), z=(r[4], r[5]), size=tuple(args.pillar_size)), max_points=args.pillar_points)
+
+
+def pfn_arguments(args):
+    """--pfn and --pfn-prefix -> (checkpoint, prefix), None without the flag; --pfn without --pillars is refused before anything is loaded"""
+    if args.pfn is None:
+        return None
+    if not args.pillars:
+        raise ValueError("--pfn needs --pillars")
+    return args.pfn, args.pfn_prefix
+
+
+def load_pfn(checkpoint, prefix, grid, device):
+    """The PillarFeatureNet of a detector checkpoint: the state dict itself, or the one under `model_state` (OpenPCDet) / `state_dict`"""
+    sd = torch.load(checkpoint, map_location="cpu")
+    for key in ("model_state", "state_dict"):
+        if isinstance(sd, dict) and key in sd and prefix + "linear.weight" not in sd:
+            sd = sd[key]
+    return PillarFeatureNet.from_state_dict(sd, prefix=prefix, grid=grid, device=device)
 
 
 def gdc_arguments(args):
@@ -217,6 +253,9 @@ def build_parser():
     ap.add_argument("--pillar-points", type=int, default=32, help="--pillars: the points kept per pillar (1..64), the first in cloud order")
     ap.add_argument("--pillar-range", nargs=6, type=float, default=(0.0, 69.12, -39.68, 39.68, -3.0, 1.0),
                     metavar=("X0", "X1", "Y0", "Y1", "Z0", "Z1"), help="--pillars: the grid's extent in the velodyne frame, metres")
+    ap.add_argument("--pfn", default=None, metavar="CHECKPOINT",
+                    help="--pillars: a detector checkpoint whose pillar feature net adds features [P, C_out] to every .npz")
+    ap.add_argument("--pfn-prefix", default="vfe.pfn_layers.0.", metavar="P", help="--pfn: where the layer sits in the state dict")
     ap.add_argument("--gdc", action="store_true",
                     help="correct every depth map against a few beams of the frame's Velodyne scan (needs datasets.groundtruth: velodyne)")
     ap.add_argument("--gdc-beams", nargs="+", type=int, default=(5, 7, 9, 11), help="--gdc: the beams of the scan's 64 that are kept")
@@ -229,6 +268,7 @@ def build_parser():
 def main(argv=None):
     args = build_parser().parse_args(argv)
     pillars = pillar_arguments(args)
+    pfn = pfn_arguments(args)
     gdc = gdc_arguments(args)
     with open(args.config) as f:
         config = yaml.full_load(f)
@@ -244,7 +284,10 @@ def main(argv=None):
         kw["beams"] = beam_tables(args.beams[0], args.beams[1])
     if gdc is not None:
         kw["gdc"] = gdc
-    n = Inference(config, args.checkpoint).export(args.out, pillars=pillars, **kw)
+    inf = Inference(config, args.checkpoint)
+    if pfn is not None:
+        kw["pfn"] = load_pfn(pfn[0], pfn[1], pillars["grid"], inf.device)
+    n = inf.export(args.out, pillars=pillars, **kw)
     print("wrote %d clouds%s under %s" % (n, " and their pillars" if pillars is not None else "", args.out))
 
 

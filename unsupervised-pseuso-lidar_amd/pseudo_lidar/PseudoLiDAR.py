@@ -19,6 +19,7 @@ tests/ground_scale_ref.py).  `project_batch(..., scale="ground")` runs it and ha
 `pillarize(points, offsets)` / `CloudBatch.pillars()` turn a cloud batch into what a LiDAR 3-D detector reads (PointPillars / SECOND /
 OpenPCDet): a `PillarBatch` of voxels [P, N, C], coords [P, 4] = (batch, z, y, x) and num_points [P] on a `PillarGrid`, the first N points
 of every non-empty cell in cloud order (mcav_pillarize; the definition is tests/pillar_ref.py).  Still nothing is read back.
+`PillarBatch.pseudo_image(net)` takes them through a detector's pillar feature net into its bird's-eye-view canvas (PillarFeatureNet.py).
 
 `gdc(depth, sparse, K)` is Pseudo-LiDAR++'s graph-based depth correction: a few exact LiDAR depths (a 4-beam scanner's, as a sparse map
 on the prediction's grid: geometry.velodyne.sparse_maps) are propagated over the predicted depth map along a windowed KNN graph of its
@@ -195,9 +196,14 @@ class PillarBatch:
         return [(self.voxels[int(o[b]):int(o[b + 1])], self.coords[int(o[b]):int(o[b + 1])], self.num_points[int(o[b]):int(o[b + 1])])
                 for b in range(len(self))]
 
-    def save_npz(self, paths):
+    def pseudo_image(self, net, **kw):
+        """net.pseudo_image(self, **kw): the batch through a PillarFeatureNet into its [B, C_out, ny, nx] canvas (layout, out, features)"""
+        return net.pseudo_image(self, **kw)
+
+    def save_npz(self, paths, features=None):
         """One device -> host copy of the used prefix (the three arrays packed on the device), then one .npz per image with `voxels`,
-        `coords` and `num_points`; coords keep the image's index within this batch in column 0."""
+        `coords` and `num_points`; coords keep the image's index within this batch in column 0.  features: a [capacity, C_out] float32
+        tensor of PillarFeatureNet.features(self); every .npz then also holds its image's rows as `features`."""
         paths = list(paths)
         if len(paths) != len(self):
             raise L.MCAVError("save_npz: %d paths for %d images" % (len(paths), len(self)))
@@ -210,10 +216,18 @@ class PillarBatch:
         vox = host[:P * N * C].view(np.float32).reshape(P, N, C)
         coords = host[P * N * C:P * N * C + 4 * P].reshape(P, 4)
         num = host[P * N * C + 4 * P:]
+        extra = None
+        if features is not None:
+            if not torch.is_tensor(features) or features.dim() != 2 or features.shape[0] < P or features.dtype != torch.float32:
+                raise L.MCAVError("save_npz: features must be float32 [>= %d, C_out]" % P)
+            extra = features[:P].cpu().numpy()
         for b, path in enumerate(paths):
             lo, hi = int(o[b]), int(o[b + 1])
+            arrays = dict(voxels=vox[lo:hi], coords=coords[lo:hi], num_points=num[lo:hi])
+            if extra is not None:
+                arrays["features"] = extra[lo:hi]
             with open(path, "wb") as f:
-                np.savez(f, voxels=vox[lo:hi], coords=coords[lo:hi], num_points=num[lo:hi])
+                np.savez(f, **arrays)
 
 
 def pillarize(points, offsets, grid=None, max_points=32, capacity=None, decorate=False, out=None):

@@ -1,2 +1,3 @@
 from .PseudoLiDAR import (BeamTables, CloudBatch, GDCResult, GroundScale, PillarBatch, PillarGrid, PseudoLiDAR, beam_tables,  # noqa: F401
                           gdc, ground_scale, pillarize)
+from .PillarFeatureNet import PillarFeatureNet  # noqa: F401
