@@ -464,6 +464,39 @@ int mcav_pillar_pseudo_image(const float* voxels, const int* coords, const int* 
                              const float* weight, const float* bias, const float* bias_pad, int c_out, int flags,
                              float* canvas, float* features /* may be null */, void* stream);
 
+/* The backward of mcav_pillar_pseudo_image: from the gradient of the canvas (and / or of the feature rows) to the gradients of the layer
+ * and, when asked for, of the voxels.  The definition is tests/pfn_bwd_ref.py; the arithmetic is csrc/pfn_bwd_math.h.  The inputs are the
+ * forward's, with the same P = min(pillar_offsets[B], capacity); nothing of the forward is kept, the layer is recomputed.
+ *   d_canvas   device, in the forward's layout (MCAV_PFN_NHWC selects it as there), or NULL
+ *   d_features device [capacity, c_out] float32, or NULL; at least one of the two is given
+ *   g          g[p, o] for p < P: d_canvas[b, o, iy, ix] when the row's (b, iy, ix) lies inside the canvas, +0.0 otherwise or without a
+ *              d_canvas; with d_features, d_features[p, o] is added to it in float32.  Elements of d_canvas at cells without a pillar are
+ *              never read.
+ *   winner     pre, act and m = feat[p, o] are the forward's, bit for bit.  Gradient flows iff m > 0 (not for a NaN; relu'(0) = 0).  It goes
+ *              to the lowest slot k < n with act(pre[p, k, o]) == m; if no used slot attains m, the padding term act(bias_pad[o]) won
+ *              (only possible with n < max_points); a tie between a slot and the padding goes to the slot.
+ *   d_weight   [c_out, columns]: d_weight[o, c] = sum over the (p, o) won by a slot of g[p, o] * voxels[p, k, c]
+ *   d_bias     [c_out]: the sum of g[p, o] over the same set;  d_bias_pad [c_out]: the sum over the (p, o) won by the padding.
+ *              Every term of the three is formed in float64 (the product of two float32 is exact there), they are added in float64 in
+ *              a fixed order and rounded once to float32.
+ *   d_voxels   device [capacity, max_points, columns] float32, or NULL: for p < P, acc = +0.0f, then for o ascending
+ *              acc = fmaf(g[p, o], weight[o, c], acc) whenever the gradient of (p, o) goes to slot k.  Every element of every row up to
+ *              capacity is written: +0.0 in slots without a winner and in rows at and beyond P.
+ * No float atomics, two runs give the same bytes; no host synchronisation, allocation or copy: the call can be captured.  Unsorted rows
+ * and rows outside the canvas never read or write outside the buffers.  2 launches.
+ * Workspace: mcav_pillar_pseudo_image_bwd_workspace_bytes (0 for sizes that are refused): 8 c_out (columns + 2) min(ceil(capacity / 64),
+ * 1024) bytes rounded up to 256, scratch of one call, no zero-fill.
+ * Returns MCAV_E_INVALID for what the forward refuses, d_canvas and d_features both null, a null d_weight, d_bias, d_bias_pad or
+ * workspace, an address that is no multiple of 4 (the workspace: of 8); MCAV_E_WORKSPACE for a short workspace; nothing is launched
+ * then. */
+size_t mcav_pillar_pseudo_image_bwd_workspace_bytes(long long capacity, int columns, int c_out);
+int mcav_pillar_pseudo_image_bwd(const float* voxels, const int* coords, const int* num_points, const int* pillar_offsets,
+                                 int B, long long capacity, int max_points, int columns, int nx, int ny,
+                                 const float* weight, const float* bias, const float* bias_pad, int c_out, int flags,
+                                 const float* d_canvas /* may be null */, const float* d_features /* may be null */,
+                                 float* d_weight, float* d_bias, float* d_bias_pad, float* d_voxels /* may be null */,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+
 /* Graph-based depth correction from sparse LiDAR (GDC): You et al., "Pseudo-LiDAR++: Accurate Depth for 3D Object Detection in Autonomous
  * Driving", ICLR 2020, section 4; the reference's notes pseudo-lidar/PL_development/research/pseudo_lidar++.md: "create a KNN graph; use
  * sparse LiDAR point clouds to bias and correct depth".  A predicted depth map has the right local shape and a smooth error; a few exact

@@ -3,7 +3,7 @@
 192 x 640 disparities (a seeded scene: tests/pl_batch_cases.py) at 375 x 1242, dense and as 64 x 512 beams (as tools/pillar_bench.py builds
 them), voxelised on PointPillars' KITTI grid (432 x 496) with N = 32 slots and the 9 decorated columns, under a seeded layer of 64 channels:
 the canvas is 12 x 64 x 496 x 432 float32 = 658 MB.
-usage: python tools/pfn_bench.py [--batch 12] [--iters 30] [--rounds 3] [--points 32] [--channels 64]
+usage: python tools/pfn_bench.py [--batch 12] [--iters 30] [--rounds 3] [--points 32] [--channels 64] [--backward]
   nchw / nhwc  PillarFeatureNet.pseudo_image(out=...) (mcav_pillar_pseudo_image: one launch), nothing read back
   features     PillarFeatureNet.features(out=...): the layer alone, no canvas
   torch        the stock formulation on the same device and inputs: F.linear over [P, N, C], the folded BatchNorm as a scale and a shift,
@@ -12,7 +12,14 @@ usage: python tools/pfn_bench.py [--batch 12] [--iters 30] [--rounds 3] [--point
 Each figure is the median of --iters per-dispatch event pairs (us) after 5 warm-up calls; the paths are alternated --rounds times in one
 session and every round is listed.  max_abs_diff: the torch canvas against the kernel's (the torch path rounds in another order, so the
 last bits differ).  bytes: what the call must move -- written: the canvas (and nothing else); read: P N C 4 + 20 P + the layer -- and the
-share of 8 TB/s they make at the nchw median; the canvas alone is the floor: a memset of it is timed beside the rest."""
+share of 8 TB/s they make at the nchw median; the canvas alone is the floor: a memset of it is timed beside the rest.
+--backward times the backward instead (mcav_pillar_pseudo_image_bwd, two launches) on the same clouds under a seeded normal canvas gradient:
+  bwd_<layout>[_vox]     PillarFeatureNet.gradients(out=...) alone, without and with d_voxels
+  fwdbwd_<layout>[_vox]  pseudo_image(out=...) followed by gradients(out=...)
+  torch_fwdbwd[_vox]     autograd through the stock formulation above, forward and backward, the parameters (and the voxels) requiring a
+                         gradient; torch_fwd is its forward with the graph recorded
+bytes: what a backward must move -- read: P N C 4 + 24 P + P C_out 4 of the gradient (an NCHW gradient comes in 32-byte sectors, so up to
+8 times that); written: capacity N C 4 for d_voxels and the slab -- and their share of 8 TB/s at the median."""
 import argparse
 import json
 import os
@@ -32,6 +39,7 @@ ap.add_argument("--iters", type=int, default=30)
 ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--points", type=int, default=32)
 ap.add_argument("--channels", type=int, default=64)
+ap.add_argument("--backward", action="store_true")
 a = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("pfn_bench: needs the GPU; a CPU run says nothing about these times")
@@ -66,8 +74,73 @@ result = {"workload": "pseudo-image B=%d %dx%d grid N=%d C=9 C_out=%d, clouds of
           "iters": a.iters, "canvas_bytes": canvas_bytes, "runs": {}}
 out_nchw = torch.empty(shape, device=dev)
 out_nhwc = torch.empty(shape, device=dev, memory_format=torch.channels_last)
+
+
+def backward_runs(kind, pb):
+    """-> the --backward entry of one cloud kind"""
+    P, cap = int(min(pb.counts()[-1], pb.voxels.shape[0])), pb.voxels.shape[0]
+    idx = pb.coords[:P].long()
+    ib, iy, ix = idx[:, 0].contiguous(), idx[:, 2].contiguous(), idx[:, 3].contiguous()
+    gen = torch.Generator(device=dev).manual_seed(9)
+    up = {"nchw": torch.randn(shape, device=dev, generator=gen)}
+    up["nhwc"] = up["nchw"].contiguous(memory_format=torch.channels_last)
+    canvas = {"nchw": out_nchw, "nhwc": out_nhwc}
+    small = [torch.empty(s, device=dev) for s in ((CO, 9), (CO,), (CO,))]
+    d_vox = torch.empty_like(pb.voxels)
+    wt, sc, sh = (t.clone().requires_grad_(True) for t in (weight, scale, shift))
+
+    def torch_form(vox_grad, backward=True):
+        v = pb.voxels[:P].detach().requires_grad_(vox_grad)
+        f = torch.relu(torch.nn.functional.linear(v, wt) * sc + sh).max(dim=1).values
+        c = torch.zeros(shape, device=dev)
+        c[ib, :, iy, ix] = f
+        if backward:
+            c.backward(up["nchw"])
+        grads = (wt.grad, sc.grad, sh.grad, v.grad)
+        wt.grad = sc.grad = sh.grad = None
+        return grads
+
+    runs = {}
+    for lay in ("nchw", "nhwc"):
+        for vox in (False, True):
+            tag = lay + ("_vox" if vox else "")
+            bwd = lambda lay=lay, vox=vox: net.gradients(pb, grad_canvas=up[lay], layout=lay, need_voxels=vox, out=small + ([d_vox] if vox else []))
+            runs["bwd_" + tag] = bwd
+            runs["fwdbwd_" + tag] = lambda lay=lay, bwd=bwd: (net.pseudo_image(pb, layout=lay, out=canvas[lay]), bwd())
+    runs.update(torch_fwd=lambda: torch_form(False, False), torch_fwdbwd=lambda: torch_form(False), torch_fwdbwd_vox=lambda: torch_form(True))
+    for fn in runs.values():
+        for _ in range(5):
+            fn()
+    rounds = {k: [] for k in runs}
+    for _ in range(a.rounds):
+        for k, fn in runs.items():
+            rounds[k].append(round(kernels(fn), 1))
+    dw, db, dp, dv = (t.clone() for t in runs["bwd_nchw_vox"]())
+    tw, ts, tsh, tv = torch_form(True)
+    same = all(bool(torch.equal(x.view(torch.int32), y.view(torch.int32))) for x, y in zip((dw, db, dp, dv), runs["bwd_nhwc_vox"]()))
+    rel = lambda x, y: float((x - y).abs().max() / y.abs().max())
+    read = P * N * 9 * 4 + P * 24 + P * CO * 4 + 4 * CO * 11
+    slab = 8 * CO * 11 * min(-(-cap // 64), 1024)
+    entry = {"pillars": P, "capacity": cap, "us_per_dispatch": {k: {"rounds": v, "median": med(v)} for k, v in rounds.items()},
+             "nhwc_equals_nchw": same, "rel_diff_to_torch": {"d_shift": rel(db + dp, tsh), "d_voxels": rel(dv[:P], tv),
+                                                              "d_weight": rel(dw, tw / scale[:, None])},
+             "bytes": {}}
+    for vox in (False, True):
+        tag = "bwd_nchw" + ("_vox" if vox else "")
+        moved = read + slab + (cap * N * 9 * 4 if vox else 0)
+        us = med(rounds[tag])
+        entry["bytes"][tag] = {"read": read, "written": moved - read, "gbytes_per_s": round(moved / us / 1e3, 1),
+                               "share_of_8TBps": round(moved / us / 1e3 / 8000.0, 4)}
+    entry["torch_fwdbwd_over_fwdbwd_nchw"] = round(med(rounds["torch_fwdbwd"]) / med(rounds["fwdbwd_nchw"]), 2)
+    entry["torch_fwdbwd_vox_over_fwdbwd_nchw_vox"] = round(med(rounds["torch_fwdbwd_vox"]) / med(rounds["fwdbwd_nchw_vox"]), 2)
+    return entry
+
+
 for kind, cb in clouds.items():
     pb = cb.pillars(grid=grid, max_points=N, decorate=True)
+    if a.backward:
+        result["runs"][kind] = backward_runs(kind, pb)
+        continue
     P = int(min(pb.counts()[-1], pb.voxels.shape[0]))
     feat = torch.empty((pb.voxels.shape[0], CO), device=dev)
     idx = pb.coords[:P].long()

@@ -5,6 +5,11 @@ over a pillar's points -- and `pseudo_image(pillars)` is that layer followed by 
 [B, C_out, ny, nx] canvas a convolutional backbone reads out, in one launch that writes every element of the canvas once
 (mcav_pillar_pseudo_image; the definition is tests/pfn_ref.py).  `from_state_dict` reads a detector checkpoint's `vfe.pfn_layers.0.*`.
 Nothing is read back.
+
+Both calls are differentiable: when grad mode is on and the weight, the bias, bias_pad or the pillars' voxels require a gradient they run
+through one torch.autograd.Function whose backward is `gradients` (mcav_pillar_pseudo_image_bwd; the definition is tests/pfn_bwd_ref.py),
+which recomputes the layer and keeps nothing of the forward.  `PillarFeatureLayer` is the torch.nn.Module with a PFNLayer's state dict
+that fine-tunes the layer on pseudo-LiDAR clouds.
 """
 import ctypes
 
@@ -17,6 +22,9 @@ from .PseudoLiDAR import PillarBatch, PillarGrid
 
 L.register({
     "mcav_pillar_pseudo_image": (L.c_i, [L.c_p] * 4 + [L.c_i, ctypes.c_longlong] + [L.c_i] * 4 + [L.c_p] * 3 + [L.c_i, L.c_i] + [L.c_p] * 3),
+    "mcav_pillar_pseudo_image_bwd_workspace_bytes": (L.c_sz, [ctypes.c_longlong, L.c_i, L.c_i]),
+    "mcav_pillar_pseudo_image_bwd": (L.c_i, [L.c_p] * 4 + [L.c_i, ctypes.c_longlong] + [L.c_i] * 4 + [L.c_p] * 3 + [L.c_i, L.c_i] + [L.c_p] * 6 +
+                                     [L.c_p, L.c_sz, L.c_p]),
 })
 
 PFN_NHWC = 1                                   # include/mcav_depth.h MCAV_PFN_NHWC
@@ -131,8 +139,12 @@ class PillarFeatureNet:
 
     def features(self, pillars, out=None):
         """-> [capacity, C_out] float32: a feature row for every pillar of the batch (rows at and beyond the pillar count are not
-        written).  out: a tensor to fill.  No canvas is made."""
+        written).  out: a tensor to fill.  No canvas is made.  Differentiable (see pseudo_image)."""
         cap, B = self._pillars(pillars, "features")
+        if self._wants_grad(pillars):
+            if out is not None:
+                raise L.MCAVError("features: out= cannot be given when a gradient is required")
+            return _PillarFunction.apply(self, pillars, None, self.weight, self.bias, self.bias_pad, pillars.voxels)
         out = torch.empty((cap, self.c_out), dtype=torch.float32, device=self.weight.device) if out is None else self._features_out(out, cap, "features")
         self._call(pillars, B, cap, 1, 1, 0, None, out)
         return out
@@ -141,10 +153,17 @@ class PillarFeatureNet:
         """-> [B, C_out, ny, nx] float32 on pillars.grid, every element written: the pillar's features in its cell, +0.0 elsewhere.
         layout: "nchw", or "nhwc": the same shape as a channels_last tensor (a torch backbone takes either).  out: a canvas of that
         shape and memory format to fill (needed under graph capture); features: a [capacity, C_out] tensor that also receives the
-        feature rows.  No host synchronisation."""
+        feature rows.  No host synchronisation.
+        Differentiable: with grad mode on and a weight, bias, bias_pad or pillars.voxels that requires a gradient the call is a node of the
+        autograd graph (out= and features= are refused then) whose backward is `gradients`; the pillars' coords, num_points and offsets
+        must still hold what they held when backward runs."""
         if layout not in ("nchw", "nhwc"):
             raise L.MCAVError("pseudo_image: layout must be 'nchw' or 'nhwc', got %r" % (layout,))
         cap, B = self._pillars(pillars, "pseudo_image", need_grid=True)
+        if self._wants_grad(pillars):
+            if out is not None or features is not None:
+                raise L.MCAVError("pseudo_image: out= and features= cannot be given when a gradient is required")
+            return _PillarFunction.apply(self, pillars, layout, self.weight, self.bias, self.bias_pad, pillars.voxels)
         grid = pillars.grid
         shape, dev = (B, self.c_out, grid.ny, grid.nx), self.weight.device
         if features is not None:
@@ -158,3 +177,134 @@ class PillarFeatureNet:
                 raise L.MCAVError("pseudo_image: out must be %s" % ("channels_last" if layout == "nhwc" else "contiguous"))
         self._call(pillars, B, cap, grid.nx, grid.ny, PFN_NHWC if layout == "nhwc" else 0, out, features)
         return out
+
+    # ------------------------------------------------------------------------------------------ the backward
+    def _wants_grad(self, pillars):
+        return torch.is_grad_enabled() and any(t.requires_grad for t in (self.weight, self.bias, self.bias_pad, pillars.voxels))
+
+    def gradients(self, pillars, grad_canvas=None, grad_features=None, layout="nchw", need_voxels=False, out=None):
+        """The backward of pseudo_image / features as a plain call (mcav_pillar_pseudo_image_bwd, two launches, no host synchronisation):
+        grad_canvas [B, C_out, ny, nx] float32 in `layout`'s memory format and / or grad_features [capacity, C_out] float32 ->
+        (d_weight [C_out, C], d_bias [C_out], d_bias_pad [C_out], d_voxels [capacity, N, C] or None), all float32.  The layer is
+        recomputed, so the slot that receives a channel's gradient is the one whose value the forward wrote.  d_voxels costs
+        capacity N C 4 bytes and is made only with need_voxels; every row of it is written, zeros behind the last pillar.
+        out: the three or four tensors to fill (needed under graph capture)."""
+        if layout not in ("nchw", "nhwc"):
+            raise L.MCAVError("gradients: layout must be 'nchw' or 'nhwc', got %r" % (layout,))
+        if grad_canvas is None and grad_features is None:
+            raise L.MCAVError("gradients: grad_canvas or grad_features must be given")
+        cap, B = self._pillars(pillars, "gradients", need_grid=grad_canvas is not None)
+        return _gradients(pillars, self.weight.detach(), self.bias.detach(), self.bias_pad.detach(), cap, B, grad_canvas, grad_features, layout,
+                          need_voxels, out)
+
+
+def _gradients(pillars, weight, bias, bias_pad, cap, B, grad_canvas, grad_features, layout, need_voxels, out):
+    dev, (c_out, columns), N = weight.device, weight.shape, pillars.voxels.shape[1]
+    nx = ny = 1
+    if grad_canvas is not None:
+        nx, ny = pillars.grid.nx, pillars.grid.ny
+        shape = (B, c_out, ny, nx)
+        if not torch.is_tensor(grad_canvas) or tuple(grad_canvas.shape) != shape or grad_canvas.device != dev or grad_canvas.dtype != torch.float32:
+            raise L.MCAVError("gradients: grad_canvas must be float32 %s on %s" % (list(shape), dev))
+        if not (grad_canvas.permute(0, 2, 3, 1) if layout == "nhwc" else grad_canvas).is_contiguous():
+            raise L.MCAVError("gradients: grad_canvas must be %s" % ("channels_last" if layout == "nhwc" else "contiguous"))
+    if grad_features is not None:
+        if not torch.is_tensor(grad_features) or tuple(grad_features.shape) != (cap, c_out) or L.dev(grad_features, "grad_features").device != dev:
+            raise L.MCAVError("gradients: grad_features must be [%d, %d] on %s" % (cap, c_out, dev))
+    shapes = [(c_out, columns), (c_out,), (c_out,)] + ([(cap, N, columns)] if need_voxels else [])
+    if out is None:
+        out = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]
+    else:
+        out = list(out)
+        if len(out) == 4 and not need_voxels:
+            out = out[:3]                                    # a d_voxels buffer that nobody asked to fill is left alone
+        if len(out) != len(shapes):
+            raise L.MCAVError("gradients: out must hold %d tensors (d_weight, d_bias, d_bias_pad%s)" % (len(shapes), ", d_voxels" if need_voxels else ""))
+        for t, s, name in zip(out, shapes, ("d_weight", "d_bias", "d_bias_pad", "d_voxels")):
+            if not torch.is_tensor(t) or tuple(t.shape) != s or L.dev(t, name).device != dev:
+                raise L.MCAVError("gradients: out's %s must be float32 %s on %s" % (name, list(s), dev))
+    hl = L.lib()
+    nbytes = hl.mcav_pillar_pseudo_image_bwd_workspace_bytes(cap, columns, c_out)
+    if nbytes == 0:
+        raise L.MCAVError("gradients: %d rows of %d columns under %d channels are refused" % (cap, columns, c_out))
+    with torch.cuda.device(dev):
+        ws = L.workspace(nbytes, dev, "pfn_bwd")
+        L.check(hl.mcav_pillar_pseudo_image_bwd(L.ptr(pillars.voxels), L.ptr(pillars.coords), L.ptr(pillars.num_points), L.ptr(pillars.offsets),
+                                                B, cap, N, columns, nx, ny, L.ptr(weight), L.ptr(bias), L.ptr(bias_pad), c_out,
+                                                PFN_NHWC if layout == "nhwc" else 0, L.ptr(grad_canvas), L.ptr(grad_features), L.ptr(out[0]),
+                                                L.ptr(out[1]), L.ptr(out[2]), L.ptr(out[3]) if need_voxels else L.c_p(0), L.ptr(ws), nbytes,
+                                                L.stream()), "mcav_pillar_pseudo_image_bwd")
+    return out[0], out[1], out[2], (out[3] if need_voxels else None)
+
+
+class _PillarFunction(torch.autograd.Function):
+    """features (layout None) or pseudo_image as one node: the forward is the call without a graph, the backward is `gradients` on the
+    saved weight, bias, bias_pad and voxels.  bias_pad being the bias itself, autograd adds the two gradients."""
+
+    @staticmethod
+    def forward(ctx, net, pillars, layout, weight, bias, bias_pad, voxels):
+        ctx.pillars, ctx.layout = pillars, layout
+        ctx.sizes = net._pillars(pillars, "backward", need_grid=layout is not None)
+        ctx.save_for_backward(weight, bias, bias_pad, voxels)
+        return net.features(pillars) if layout is None else net.pseudo_image(pillars, layout=layout)        # grad mode is off in here
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        weight, bias, bias_pad, voxels = ctx.saved_tensors
+        if voxels.data_ptr() != ctx.pillars.voxels.data_ptr():
+            raise L.MCAVError("backward: the PillarBatch's voxels were replaced after the forward")
+        cap, B = ctx.sizes
+        grad = grad.to(torch.float32)
+        if ctx.layout is None:
+            canvas, feats, layout = None, grad.contiguous(), "nchw"
+        else:
+            layout = ctx.layout
+            canvas, feats = grad.contiguous(memory_format=torch.channels_last if layout == "nhwc" else torch.contiguous_format), None
+        dw, db, dp, dv = _gradients(ctx.pillars, weight, bias, bias_pad, cap, B, canvas, feats, layout, ctx.needs_input_grad[6], None)
+        return None, None, None, dw, db, dp, dv
+
+
+class PillarFeatureLayer(torch.nn.Module):
+    """PointPillars' PFNLayer as a trainable module on the fused kernels: submodules `linear` (no bias) and `norm` (BatchNorm1d), so the
+    state dict is a PFNLayer's -- linear.weight, norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.num_batches_tracked --
+    and a detector checkpoint's `vfe.pfn_layers.0.*` loads and saves.  in_columns: 4 or 9 (a PillarBatch's columns), or OpenPCDet's 10
+    with the PillarGrid whose z range gives the tenth column's zc (the pillars still hold 9 columns); out_channels in 32, 64, 96, 128.
+
+    forward(pillars, layout) folds the BatchNorm with its RUNNING statistics into the layer in differentiable float64 torch ops
+    (PillarFeatureNet.fold_state_dict's formulas, rounded once to float32) and calls PillarFeatureNet.pseudo_image, whose backward is the
+    HIP kernel.  This is frozen-statistics fine-tuning: linear.weight, norm.weight and norm.bias learn; running_mean and running_var are
+    never updated, in train() as in eval(), and batch statistics over the pillars' points are not computed."""
+
+    def __init__(self, in_columns=9, out_channels=64, eps=1e-3, grid=None):
+        super().__init__()
+        if in_columns not in COLUMNS + (10,) or out_channels not in OUT_CHANNELS:
+            raise L.MCAVError("PillarFeatureLayer: in_columns must be 4, 9 or 10 and out_channels in %s, got %r and %r"
+                              % (OUT_CHANNELS, in_columns, out_channels))
+        if in_columns == 10 and not isinstance(grid, PillarGrid):
+            raise L.MCAVError("PillarFeatureLayer: 10 columns (z - zc) need the PillarGrid whose z range gives zc")
+        self.in_columns, self.out_channels, self.eps, self.grid = in_columns, out_channels, float(eps), grid
+        self.linear = torch.nn.Linear(in_columns, out_channels, bias=False)
+        self.norm = torch.nn.BatchNorm1d(out_channels, eps=eps)
+
+    def folded(self):
+        """-> weight [C_out, C], bias, bias_pad (None: the bias itself) as float32 tensors with the parameters' graph behind them"""
+        w = self.linear.weight.double()
+        scale = self.norm.weight.double() / torch.sqrt(self.norm.running_var.double() + self.eps)
+        wf = w * scale[:, None]
+        bf = self.norm.bias.double() + (0.0 - self.norm.running_mean.double()) * scale
+        if self.in_columns != 10:
+            return wf.float().contiguous(), bf.float(), None
+        zc = (self.grid.z[0] + self.grid.z[1]) / 2.0
+        bias = bf - wf[:, 9] * zc
+        wf = torch.cat([wf[:, :2], (wf[:, 2] + wf[:, 9])[:, None], wf[:, 3:9]], dim=1)
+        return wf.float().contiguous(), bias.float(), bf.float()
+
+    def forward(self, pillars, layout="nchw"):
+        """-> the pseudo-image [B, C_out, ny, nx] of PillarFeatureNet.pseudo_image under the folded layer"""
+        return PillarFeatureNet(*self.folded()).pseudo_image(pillars, layout=layout)
+
+    def eval_net(self):
+        """-> the PillarFeatureNet of the current parameters, without a graph"""
+        with torch.no_grad():
+            return PillarFeatureNet(*[None if t is None else t.detach() for t in self.folded()])

@@ -1,3 +1,3 @@
 from .PseudoLiDAR import (BeamTables, CloudBatch, GDCResult, GroundScale, PillarBatch, PillarGrid, PseudoLiDAR, beam_tables,  # noqa: F401
                           gdc, ground_scale, pillarize)
-from .PillarFeatureNet import PillarFeatureNet  # noqa: F401
+from .PillarFeatureNet import PillarFeatureLayer, PillarFeatureNet  # noqa: F401
