@@ -51,7 +51,11 @@ typedef struct mcav_igemm_desc {
     int kh, kw, Np, Kp;
     int mode, stride, sign, offset, pad_mode;
     /* destination: logical [B, Hd, Wd, *]; this launch computes filter rows [n_begin, n_begin + n_count) and writes
-     * them to channels [y_choff, y_choff + n_count) of y, whose pixel stride is Cd floats */
+     * them to channels [y_choff, y_choff + n_count) of y, whose pixel stride is Cd floats.  Refused (MCAV_E_INVALID, nothing launched):
+     * Cd <= 0, y_choff < 0, y_choff + n_count > Cd (the launch would spill into the next pixel), and a destination of 2^31 - 1 bytes or
+     * more -- B * Hd * Wd * Cd * 4, with pool B * (Hd / 2) * (Wd / 2) * Cd * 4: the kernels address y, dact_aux, addend and stats_x through
+     * 32-bit byte offsets.  A kernel form that does not store sub-ranges (the halo and stem kernels with y_choff != 0, the K-split with
+     * n_count != Cd) hands the launch to one that does. */
     float* y;
     int Hd, Wd, Cd, n_begin, n_count, y_choff;
     /* epilogue, in this order: + bias[n]; activation; * act'(dact_aux) ; + addend; 2x2 sum pooling */
@@ -126,7 +130,9 @@ typedef struct mcav_wgrad_desc {
     int B, Hs, Ws, C1, C2, up1;
     int kh, kw, Kp;
     int mode, stride, sign, offset, pad_mode;
-    const float* dy;        /* [B, Hd, Wd, Cdy], channels [dy_choff, dy_choff + Cout) are used */
+    const float* dy;        /* [B, Hd, Wd, Cdy], channels [dy_choff, dy_choff + Cout) are used.  Refused (workspace size 0, MCAV_E_INVALID, nothing
+                             * launched): Cdy <= 0, dy_choff < 0, dy_choff + Cout > Cdy; kh <= 0 or kw <= 0; and, with Cin_total / ci_offset
+                             * below, ci_offset < 0 or ci_offset + Cin > Cin_total (Cin_total = 0 stands for Cin) */
     int Hd, Wd, Cdy, dy_choff;
     int Cout, Cin;          /* true channel counts of the OIHW gradient */
     float* dw_oihw;

@@ -23,47 +23,13 @@ import torch
 
 import nn_ops_cases as K
 import nn_ops_ref as R
+from guarded import SENT8, SENT32, Guarded, P, bits, same_bits  # noqa: F401  (the window helpers, shared with the conv modules)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 U = 2.0 ** -24
-GUARD = 64                       # elements on each side (256 bytes of float32: the windows stay 16-byte aligned)
-SENT32 = 0x7FA5A5A5              # a NaN
-SENT8 = 0xA5
 E_INVALID, E_WORKSPACE = -1, -2
 F32 = torch.float32
-
-
-def P(t):
-    if isinstance(t, Guarded):
-        t = t.t
-    return t.data_ptr() if t is not None else None
-
-
-class Guarded:
-    """A float32 / uint8 output window of `shape` inside a larger allocation filled with sentinels; init: what the window starts with."""
-
-    def __init__(self, shape, dtype=F32, init=None):
-        n = int(np.prod(shape))
-        self.buf = torch.empty(n + 2 * GUARD, dtype=dtype, device=DEV)
-        self.sent = SENT32 if dtype == F32 else SENT8
-        self.raw().fill_(self.sent)
-        self.t = self.buf[GUARD:GUARD + n].view(shape)
-        if init is not None:
-            self.t.copy_(init)
-
-    def raw(self):
-        return self.buf.view(torch.int32) if self.buf.dtype == F32 else self.buf
-
-    def intact(self):
-        r = self.raw()
-        return bool((r[:GUARD] == self.sent).all()) and bool((r[-GUARD:] == self.sent).all())
-
-    def untouched(self):
-        return bool((self.raw() == self.sent).all())
-
-    def cpu(self):
-        return self.t.detach().cpu()
 
 
 def call(name, *args, outs=(), expect=0):
@@ -80,15 +46,6 @@ def call(name, *args, outs=(), expect=0):
 
 def dev(t):
     return t.contiguous().to(DEV)
-
-
-def bits(t):
-    t = t.detach().cpu().contiguous()
-    return t.view(torch.int32) if t.dtype == F32 else t
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and torch.equal(bits(a), bits(b))
 
 
 def three_col(name, hip, cpu32, ref64, mag, ops):

@@ -10,25 +10,39 @@ import ctypes
 import pytest
 import torch
 
+from guarded import guard_allocations, guarded_spec
 from test_stem_fused_gpu import BN, make_case, same_bits
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 E_INVALID = -1
+# the whole networks keep torch.empty (the windows would keep every activation alive)
+UNGUARDED = ("test_whole_networks_keep_every_gradient_and_buffer_bit_for_bit",)
+
+
+@pytest.fixture(autouse=True)
+def guarded_outputs(request):
+    """Every mcav.nn.empty() of a kernel-level test is a NaN-filled window between sentinel bands (tests/guarded.py), checked after the test."""
+    if request.node.originalname in UNGUARDED:
+        yield
+        return
+    with guard_allocations() as guards:
+        yield
+        guards.check()
 
 
 def depth_spec(seed):
     from mcav import nn as N
     g = torch.Generator().manual_seed(seed)
     w = torch.randn(64, 3, 7, 7, generator=g) * 0.1 * torch.exp(1.5 * torch.randn(64, 1, 1, 1, generator=g))
-    return N.ConvSpec(torch.nn.Parameter(w.to(DEV)), None, 2, 3, 0, smallc=True)
+    return guarded_spec(N.ConvSpec(torch.nn.Parameter(w.to(DEV)), None, 2, 3, 0, smallc=True))
 
 
 def pose_spec(seed):
     from mcav import nn as N
     g = torch.Generator().manual_seed(seed)
     w = torch.randn(16, 9, 7, 7, generator=g) * 0.1 * torch.exp(1.5 * torch.randn(16, 1, 1, 1, generator=g))
-    return N.ConvSpec(torch.nn.Parameter(w.to(DEV)), torch.nn.Parameter(torch.randn(16, generator=g).to(DEV)), 2, 3, 0)
+    return guarded_spec(N.ConvSpec(torch.nn.Parameter(w.to(DEV)), torch.nn.Parameter(torch.randn(16, generator=g).to(DEV)), 2, 3, 0))
 
 
 def images(n, Bp, H, W, seed):
@@ -184,7 +198,7 @@ def test_bn_fields_are_refused_outside_the_depth_stem():
     from mcav import nn as N
     coeffs = torch.ones(2 * 64, device=DEV)
     # a 3x3 layer
-    spec = N.ConvSpec(torch.nn.Parameter(torch.zeros(64, 64, 3, 3, device=DEV)), None, 1, 1, 0)
+    spec = guarded_spec(N.ConvSpec(torch.nn.Parameter(torch.zeros(64, 64, 3, 3, device=DEV)), None, 1, 1, 0))
     x, dy = torch.ones(1, 8, 8, 64, device=DEV), torch.ones(1, 8, 8, 64, device=DEV)
     d = wgrad_desc(spec, x, dy)
     assert N.L.lib().mcav_wgrad_workspace_bytes(ctypes.byref(d)) > 0               # launchable without the fields
@@ -212,7 +226,7 @@ def test_bn_fields_are_refused_outside_the_depth_stem():
 def test_planar_fields_are_refused_outside_the_stems():
     from mcav import lib as L
     from mcav import nn as N
-    spec = N.ConvSpec(torch.nn.Parameter(torch.ones(64, 64, 3, 3, device=DEV)), None, 1, 1, 0)
+    spec = guarded_spec(N.ConvSpec(torch.nn.Parameter(torch.ones(64, 64, 3, 3, device=DEV)), None, 1, 1, 0))
     x, y = torch.ones(1, 8, 8, 64, device=DEV), torch.zeros(1, 8, 8, 64, device=DEV)
     img = torch.ones(1, 3, 8, 8, device=DEV)
     d = N.IgemmDesc()

@@ -1809,12 +1809,25 @@ void tile_dims(int id, int& BM, int& BN) {
     }
 }
 
+// a * b * c * e < 2^31 - 1 for positive factors, without overflowing on the way
+inline bool bytes_fit_31(long a, long b, long c, long e) {
+    const long lim = 0x7fffffffL;
+    if (a <= 0 || b <= 0 || c <= 0 || e <= 0) return false;
+    if (a >= lim / b) return false;
+    a *= b;
+    if (a >= lim / c) return false;
+    a *= c;
+    return a < lim / e;
+}
+
 bool fill_params(const mcav_igemm_desc* d, IgemmParams& p, int& tile) {
     if (!d || !d->x1 || !d->w || !d->y) return false;
     if (d->B <= 0 || d->Hs <= 0 || d->Ws <= 0 || d->Hd <= 0 || d->Wd <= 0 || d->C1 <= 0 || d->C2 < 0) return false;
     if (d->C2 > 0 && !d->x2) return false;
     if (d->kh <= 0 || d->kw <= 0 || d->Np <= 0 || d->Kp <= 0 || d->kh * d->kw > 64) return false;
     if (d->n_begin < 0 || d->n_count <= 0 || d->n_begin + d->n_count > d->Np) return false;
+    // the destination: channels [y_choff, y_choff + n_count) of a pixel of Cd floats (a launch that ran past Cd would spill into the next pixel)
+    if (d->Cd <= 0 || d->y_choff < 0 || d->y_choff > d->Cd - d->n_count) return false;
     if (d->mode == MCAV_G_SMALLC) { if (d->Kp != 4 || d->C1 != 4 || d->C2 != 0) return false; }
     else if (d->Kp % CK != 0 || d->Kp < d->C1 + d->C2) return false;
     if (d->C2 > 0 && (d->C1 % 4 != 0)) return false;
@@ -1833,6 +1846,9 @@ bool fill_params(const mcav_igemm_desc* d, IgemmParams& p, int& tile) {
     const long Mlin = (long)d->B * d->Hd * d->Wd;
     if ((long)d->B * d->Hs * d->Ws * (d->C1 > d->C2 ? d->C1 : d->C2) * 4 >= 0x7fffffffL) return false;   // 32-bit byte offsets
     if ((long)d->Np * kstride_of(d->kh * d->kw, d->Kp) * 4 >= 0x7fffffffL) return false;
+    // ... and so has the destination (the pooled one where pool is set): the lean epilogue, the halo and the stem kernels address y -- and
+    // dact_aux, addend, stats_x, which share its layout -- through 32-bit byte offsets
+    if (!bytes_fit_31((long)d->B, d->pool ? d->Hd >> 1 : d->Hd, d->pool ? d->Wd >> 1 : d->Wd, (long)d->Cd * 4)) return false;
     p.no_tab = (d->tile >> 8) & 1;
     p.ksplit = 1; p.kslab = nullptr;
     p.wm = d->w_upmerge; p.Np_all = d->Np; p.upm = 0;
@@ -2048,6 +2064,9 @@ bool plan_wgrad(const mcav_wgrad_desc* d, WgradPlan& pl) {
     if (d->mode == MCAV_G_SMALLC && (d->Kp != 4 || d->C1 != 4 || d->C2 != 0)) return false;
     if (d->mode == MCAV_G_DIRECT && (d->Kp % CK != 0 || d->Kp < d->C1 + d->C2)) return false;
     if (d->Cin > d->Kp) return false;
+    if (d->kh <= 0 || d->kw <= 0) return false;
+    if (d->Cdy <= 0 || d->dy_choff < 0 || d->dy_choff > d->Cdy - d->Cout) return false;      // channels [dy_choff, dy_choff + Cout) of dy exist
+    if (d->ci_offset < 0 || d->ci_offset > (d->Cin_total > 0 ? d->Cin_total : d->Cin) - d->Cin) return false;      // the launch's input-channel window lies inside the OIHW gradient
     WgradParams& p = pl.p;
     p.g.x1 = d->x1; p.g.x2 = d->x2; p.g.B = d->B; p.g.Hs = d->Hs; p.g.Ws = d->Ws; p.g.C1 = d->C1; p.g.C2 = d->C2; p.g.up1 = d->up1;
     p.g.mode = d->mode; p.g.stride = d->stride; p.g.sign = d->sign; p.g.offset = d->offset; p.g.pad_mode = d->pad_mode;
@@ -2204,8 +2223,6 @@ static int wgrad_gemm(const mcav_wgrad_desc* d, void* workspace, size_t workspac
     if ((!bf16 && !plan_wgrad(d, pl)) || !workspace) return MCAV_E_INVALID;
     if ((bn || planar) && !pl.use_stem) return MCAV_E_INVALID;
     if (workspace_bytes < pl.slab_bytes + pl.pre_bytes) return MCAV_E_WORKSPACE;
-    const int cin_total = d->Cin_total > 0 ? d->Cin_total : d->Cin;
-    if (d->ci_offset < 0 || d->ci_offset + d->Cin > cin_total) return MCAV_E_INVALID;
     pl.p.slab = reinterpret_cast<float*>(workspace);
     if (bf16) mcav_bf16_wgrad_launch(pl.p, s);
     else if (pl.use_stem) mcav_stem_wgrad_launch(d, pl.p.slab, pl.p.Ktot, pl.p.slabN, pl.p.splits, s);
