@@ -184,6 +184,55 @@ size_t mcav_wgrad_workspace_bytes(const mcav_wgrad_desc* d);
 int mcav_wgrad_uses_bf16(const mcav_wgrad_desc* d);
 int mcav_wgrad(const mcav_wgrad_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Route query: which kernel family a descriptor takes and in which form, as planned by the one planner (csrc/conv_plan.h) that mcav_igemm,
+ * mcav_igemm_mtiles, mcav_wgrad, mcav_wgrad_deferred, mcav_wgrad_workspace_bytes and mcav_wgrad_uses_bf16 launch and answer from.  Both calls
+ * only plan: no tensor pointer is dereferenced and nothing is launched (pointers must be non-null where the launch needs them).  Return
+ * MCAV_OK, or MCAV_E_INVALID for a descriptor the launch refuses (*out is then zeroed).
+ * The families are asked in the order of these enums' comments; the first that accepts takes the launch. */
+enum mcav_igemm_family {
+    MCAV_IGEMM_FP32 = 0,         /* asked last: the table-driven / fast / generic fp32 MFMA tile kernels (conv_igemm.hip), any descriptor */
+    MCAV_IGEMM_HALO = 1,         /* 1st: narrow high-resolution 3x3 layers, forward and reflect-adjoint (conv_halo.hip); tile bit 9 opts out */
+    MCAV_IGEMM_STEM = 2,         /* 2nd (alone where the source is planar): the 7x7 stride-2 stems with w_stem (conv_stem.hip); tile bit 9 opts out */
+    MCAV_IGEMM_PATCH_F32 = 3,    /* 3rd, opt-in (tile bit 13), mma = 0: the fp32 patch-in-LDS kernel (conv_bf16.hip) */
+    MCAV_IGEMM_BF16_PATCH3 = 4,  /* 4th, opt-in (tile low byte 0x33), mma >= 2: the twelve-wavefront patch kernel */
+    MCAV_IGEMM_BF16_PATCH2 = 5,  /* 5th, opt-in (tile bits 14 / 15), mma >= 2: the second patch kernel */
+    MCAV_IGEMM_BF16_PATCH = 6,   /* 6th, mma != 0: the patch-in-LDS kernel (3x3 stride 1, one source) */
+    MCAV_IGEMM_BF16_TILE = 7     /* 7th, mma = 1 or 3: the table-driven bf16 MFMA tiles */
+};                               /* mcav_igemm_uses_bf16() == 1 exactly for the four BF16 families */
+enum mcav_wgrad_family {
+    MCAV_WGRAD_FP32 = 0,         /* asked last: the fp32 slab GEMM tiles (conv_igemm.hip) */
+    MCAV_WGRAD_HALO = 1,         /* 3rd: the narrow 3x3 layers' kernel writes the slab (conv_halo.hip) */
+    MCAV_WGRAD_STEM = 2,         /* 4th, overriding the halo kernel (alone with dy_bn_* or planar sources): the 7x7 stride-2 stems' kernel (conv_stem.hip) */
+    MCAV_WGRAD_BF16_PATCH = 3,   /* 1st, mma != 0: wgrad3x3_patch_kernel */
+    MCAV_WGRAD_BF16_TILE = 4     /* 2nd, mma = 1 or 3: the table-driven bf16 slab GEMM */
+};                               /* mcav_wgrad_uses_bf16() == 1 exactly for the two BF16 families */
+/* mcav_conv_route.variant: the form within the family, an OR of */
+#define MCAV_RV_ADJ 0x1          /* an adjoint (data-gradient) kernel form */
+#define MCAV_RV_REFLECT 0x2      /* reflection padding resolved by the kernel (with ADJ: its adjoint) */
+#define MCAV_RV_UPM 0x4          /* merged-tap upsample: 4 taps on the low-resolution source */
+#define MCAV_RV_PLANAR 0x8       /* the stem reads the NCHW images (x_planar) */
+#define MCAV_RV_LEAN 0x10        /* the stem stores through the shared 4-byte-store epilogue (tile bit 16; PoseNet's stem always) */
+#define MCAV_RV_SPLIT 0x20       /* fp32 contraction on three bf16 planes per operand */
+#define MCAV_RV_TMB2 0x40        /* patch kernel: 128-pixel blocks */
+#define MCAV_RV_K64 0x80         /* bf16 tiles: 64-deep K-tiles */
+#define MCAV_RV_SB4 0x100        /* second patch kernel: four sub-blocks per workgroup (else two) */
+#define MCAV_RV_BN32 0x200       /* second patch kernel: 128 x 32 tiles */
+#define MCAV_RV_TABLE 0x400      /* offset-table kernel (else the fast or generic gather) */
+#define MCAV_RV_FAST 0x800       /* branch-free 16-byte gather without a table */
+#define MCAV_RV_BN_FOLD 0x1000   /* stem weight gradient: BatchNorm backward folded into the dy load */
+#define MCAV_RV_POSE 0x2000      /* PoseNet's stem (else the depth net's) */
+typedef struct mcav_conv_route {
+    int family;                  /* mcav_igemm_family / mcav_wgrad_family */
+    int variant;                 /* MCAV_RV_* */
+    int tile;                    /* tile-config id the rows are laid out for */
+    int mtiles, ntiles;          /* igemm: rows of `stats` (= mcav_igemm_mtiles) and column tiles; wgrad: slab tiles along Ktot and Cout */
+    int workgroups;              /* of the main launch as planned (a K-split whose slab cannot be allocated launches fewer) */
+    int splits;                  /* wgrad: slab partials; igemm: the planned K-split (1 = none) */
+    size_t workspace_bytes;      /* wgrad: = mcav_wgrad_workspace_bytes; igemm: 0 */
+} mcav_conv_route;
+int mcav_igemm_route(const mcav_igemm_desc* d, mcav_conv_route* out);
+int mcav_wgrad_route(const mcav_wgrad_desc* d, mcav_conv_route* out);
+
 /* Batched slab reduction.  mcav_wgrad = GEMM (partial tiles of the pixel splits into a slab) + one or two reduction launches per layer: 68
  * small launches per step for ResNet-18 + PoseNet.  mcav_wgrad_deferred runs the GEMM only and describes the pending reduction in *item (HOST
  * memory; the workspace must stay untouched until it has been reduced: one workspace per pending layer).  The caller collects the items of a

@@ -5,6 +5,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_err
+from conv_plan_cases import recorded_routes
 from guarded import guard_allocations, guarded_spec
 
 pytestmark = pytest.mark.gpu
@@ -201,17 +202,25 @@ def test_decoder_level_fused_upsample_concat(dims):
     pre.backward(dy)
     wp, bp = torch.nn.Parameter(wt.detach().to(DEV)), torch.nn.Parameter(bs.detach().to(DEV))
     spec = guarded_spec(N.ConvSpec(wp, bp, 1, 1, 1))
-    got = N.conv_fwd(spec, nhwc(a.detach()), nhwc(skip.detach()), up1=True, act=N.ACT_ELU)            # merged-tap upsample path
+    with recorded_routes(N) as routes:
+        got = N.conv_fwd(spec, nhwc(a.detach()), nhwc(skip.detach()), up1=True, act=N.ACT_ELU)        # merged-tap upsample path
     assert rel_err(nchw(got), want) < 2e-5
+    assert [(k, r.family, r.variant) for k, r in routes] == [("fwd", N.IGEMM_FP32, N.RV_TABLE | N.RV_UPM)]
     for tile in (0x800, 10, 0x800 | 10, 12, 1):       # the nine-tap path (bit 11), and both under 32-deep / 32-row / 128-row tiles
-        got = N.conv_fwd(spec, nhwc(a.detach()), nhwc(skip.detach()), up1=True, act=N.ACT_ELU, tile=tile)
+        with recorded_routes(N) as routes:
+            got = N.conv_fwd(spec, nhwc(a.detach()), nhwc(skip.detach()), up1=True, act=N.ACT_ELU, tile=tile)
         assert rel_err(nchw(got), want) < 2e-5, hex(tile)
+        assert [(k, r.family, r.variant) for k, r in routes] == [("fwd", N.IGEMM_FP32, N.RV_TABLE | (0 if tile & 0x800 else N.RV_UPM))], hex(tile)
     dyd = nhwc(dy)
-    N.conv_wgrad(spec, nhwc(a.detach()), dyd, x2=nhwc(skip.detach()), up1=True, tile=0x1000)   # skip half + merged-tap upsampled half (bit 12)
+    with recorded_routes(N) as routes:
+        N.conv_wgrad(spec, nhwc(a.detach()), dyd, x2=nhwc(skip.detach()), up1=True, tile=0x1000)   # skip half + merged-tap upsampled half (bit 12)
+    assert [(k, r.family, r.variant) for k, r in routes] == [("wgrad", N.WGRAD_FP32, N.RV_TABLE), ("wgrad", N.WGRAD_FP32, N.RV_TABLE | N.RV_UPM)]
     assert rel_err(wp.grad, wt.grad) < 5e-5 and rel_err(bp.grad, bs.grad) < 5e-5
     assert rel_err(wp.grad[:, :C1], wt.grad[:, :C1]) < 5e-5 and rel_err(wp.grad[:, C1:], wt.grad[:, C1:]) < 5e-5
     guarded_spec(spec)                                # fresh zeroed gradient windows
-    N.conv_wgrad(spec, nhwc(a.detach()), dyd, x2=nhwc(skip.detach()), up1=True, tile=0x800)   # one ordinary launch (bit 11)
+    with recorded_routes(N) as routes:
+        N.conv_wgrad(spec, nhwc(a.detach()), dyd, x2=nhwc(skip.detach()), up1=True, tile=0x800)   # one ordinary launch (bit 11)
+    assert [(k, r.family, r.variant) for k, r in routes] == [("wgrad", N.WGRAD_FP32, N.RV_TABLE)]
     assert rel_err(wp.grad, wt.grad) < 5e-5 and rel_err(bp.grad, bs.grad) < 5e-5
     da = N.conv_dgrad(spec, dyd, (2 * h, 2 * w_), n_begin=0, n_count=C1, pool=True)
     assert rel_err(nchw(da), a.grad) < 2e-5
@@ -265,8 +274,10 @@ def test_stem_patch_kernels_forward_stats_wgrad(B, H, W):
     spec = guarded_spec(N.ConvSpec(wp, None, 2, 3, 0, smallc=True))
     x4 = N.nchw_to_nhwc(x.to(DEV), 4)
     groups = 2 if B % 2 == 0 else 1
-    got, slab = N.conv_fwd(spec, x4, stats=True, groups=groups)
+    with recorded_routes(N) as routes:
+        got, slab = N.conv_fwd(spec, x4, stats=True, groups=groups)
     assert getattr(spec, "_stem", None) is not None, "the stem launch did not take the patch kernel"
+    assert [(k, r.family, r.variant, r.mtiles) for k, r in routes] == [("fwd", N.IGEMM_STEM, 0, slab.shape[0])]
     assert rel_err(nchw(got), y) < 2e-5
     mt = slab.shape[0] // groups
     assert mt == (B // groups) * (-(-y.shape[2] // 8)) * (-(-y.shape[3] // 32))
@@ -275,9 +286,11 @@ def test_stem_patch_kernels_forward_stats_wgrad(B, H, W):
         part = y.detach()[grp * (B // groups):(grp + 1) * (B // groups)]
         assert rel_err(s_[0], part.sum((0, 2, 3))) < 1e-4
         assert rel_err(s_[1], (part ** 2).sum((0, 2, 3))) < 1e-4
-    old = N.conv_fwd(spec, x4, tile=0x200)
+    with recorded_routes(N) as routes:
+        old = N.conv_fwd(spec, x4, tile=0x200)
+        N.conv_wgrad(spec, x4, nhwc(dy))
+    assert [(k, r.family) for k, r in routes] == [("fwd", N.IGEMM_FP32), ("wgrad", N.WGRAD_STEM)]      # bit 9: the general kernels
     assert rel_err(got, old) < 2e-5
-    N.conv_wgrad(spec, x4, nhwc(dy))
     assert rel_err(wp.grad, w.grad) < 5e-5
     N.conv_wgrad(spec, x4, nhwc(dy))                  # accumulates
     assert rel_err(wp.grad, 2 * w.grad) < 5e-5
@@ -298,11 +311,15 @@ def test_pose_stem_patch_kernels(B, H, W):
     wp, bp = torch.nn.Parameter(w.detach().to(DEV)), torch.nn.Parameter(b.detach().to(DEV))
     spec = guarded_spec(N.ConvSpec(wp, bp, 2, 3, 0))
     xin = nhwc(x, 16)
-    got = N.conv_fwd(spec, xin, act=N.ACT_RELU)
+    with recorded_routes(N) as routes:
+        got = N.conv_fwd(spec, xin, act=N.ACT_RELU)
+        old = N.conv_fwd(spec, xin, act=N.ACT_RELU, tile=0x200)
+        N.conv_wgrad(spec, xin, nhwc(dy))
+    assert [(k, r.family, r.variant) for k, r in routes] == [("fwd", N.IGEMM_STEM, N.RV_POSE | N.RV_LEAN), ("fwd", N.IGEMM_FP32, routes[1][1].variant),
+                                                             ("wgrad", N.WGRAD_STEM, N.RV_POSE)]
     assert getattr(spec, "_stem", None) is not None, "the launch did not take the patch kernel"
     assert rel_err(nchw(got), F.relu(pre)) < 2e-5
-    assert rel_err(got, N.conv_fwd(spec, xin, act=N.ACT_RELU, tile=0x200)) < 2e-5
-    N.conv_wgrad(spec, xin, nhwc(dy))
+    assert rel_err(got, old) < 2e-5
     assert rel_err(wp.grad, w.grad) < 5e-5
     assert rel_err(bp.grad, b.grad) < 5e-5
     N.conv_wgrad(spec, xin, nhwc(dy))                  # accumulates
@@ -422,13 +439,27 @@ def test_halo_kernel_fused_upsample():
         spec = N.ConvSpec(torch.nn.Parameter(wt.detach().to(DEV)), torch.nn.Parameter(bs.detach().to(DEV)), 1, 1, N.PAD_REFLECT)
         ad = nhwc(a.detach())
         for tile in (0, 0x400, 0x200):                  # merged-tap halo kernel (forward), the 9-tap halo kernel, the general kernels
-            got = N.conv_fwd(spec, ad, None, up1=True, act=N.ACT_ELU, tile=tile)
+            with recorded_routes(N) as routes:
+                got = N.conv_fwd(spec, ad, None, up1=True, act=N.ACT_ELU, tile=tile)
             assert rel_err(nchw(got), want) < 2e-5
-            da = N.conv_dgrad(spec, nhwc(dy), (2 * h, 2 * w_), n_begin=0, n_count=C, dact_aux=ad, dact=N.ACT_ELU, addend=nhwc(addend),
-                              pool=True, tile=tile)
+            with recorded_routes(N) as routes_d:
+                da = N.conv_dgrad(spec, nhwc(dy), (2 * h, 2 * w_), n_begin=0, n_count=C, dact_aux=ad, dact=N.ACT_ELU, addend=nhwc(addend),
+                                  pool=True, tile=tile)
             assert rel_err(nchw(da), pre_a.grad + addend) < 2e-5
             guarded_spec(spec)                            # weight / bias gradient: merged-tap halo kernel, plain halo kernel, general kernel
-            N.conv_wgrad(spec, ad, nhwc(dy), up1=True, tile=tile)
+            with recorded_routes(N) as routes_w:
+                N.conv_wgrad(spec, ad, nhwc(dy), up1=True, tile=tile)
+            # which kernels the planner names: bit 9 (0x200) opts out of the halo kernels, bit 10 (0x400) of their merged-tap forms
+            general = tile == 0x200
+            assert [(k, r.family, r.variant & N.RV_UPM) for k, r in routes] == [("fwd", N.IGEMM_FP32 if general else N.IGEMM_HALO, 0 if tile else N.RV_UPM)]
+            (kind, r), = routes_d
+            if kind == "dgrad":                           # (32 -> 32: the 4x4 stride-2 form of the pooled adjoint instead, on the general kernels)
+                assert (r.family, r.variant & N.RV_ADJ) == (N.IGEMM_FP32 if general else N.IGEMM_HALO, N.RV_ADJ), (hex(tile), r.family, r.variant)
+            else:
+                assert (C, Cout, r.family) == (32, 32, N.IGEMM_FP32), (hex(tile), kind, r.family)
+            halo_w = not general and not (C == 32 and Cout > 16)          # (32 -> 32 would hold 144 filter registers per lane)
+            assert [(k, r.family, r.variant & N.RV_UPM) for k, r in routes_w] == [
+                ("wgrad", N.WGRAD_HALO if halo_w else N.WGRAD_FP32, N.RV_UPM if halo_w and not tile and (C, Cout) == (16, 16) else 0)], hex(tile)
             assert rel_err(spec.weight.grad, wt.grad) < 5e-5 and rel_err(spec.bias.grad, bs.grad) < 5e-5, hex(tile)
 
 
@@ -512,12 +543,16 @@ def test_fp32_patch_in_lds_kernel_matches_the_table_driven_one(case):
     spec = N.ConvSpec(torch.nn.Parameter(w.to(DEV)), torch.nn.Parameter(b.to(DEV)), 1, 1, N.PAD_ZERO)
     PATCH = 1 << 13
     want = F.relu(F.conv2d(x.double(), w.double(), b.double(), padding=1))
-    got = N.conv_fwd(spec, nhwc(x), act=N.ACT_RELU, tile=PATCH)
-    ref = N.conv_fwd(spec, nhwc(x), act=N.ACT_RELU)
+    with recorded_routes(N) as routes:
+        got = N.conv_fwd(spec, nhwc(x), act=N.ACT_RELU, tile=PATCH)
+        ref = N.conv_fwd(spec, nhwc(x), act=N.ACT_RELU)
+    assert [(k, r.family) for k, r in routes] == [("fwd", N.IGEMM_PATCH_F32), ("fwd", N.IGEMM_FP32)]
     assert rel_err(nchw(got), want) < 2e-6 and rel_err(nchw(got), nchw(ref)) < 2e-6
     nob = N.ConvSpec(spec.weight, None, 1, 1, N.PAD_ZERO)
     G = 2 if B % 2 == 0 else 1
-    y, slab = N.conv_fwd(nob, nhwc(x), stats=True, groups=G, tile=PATCH)
+    with recorded_routes(N) as routes:
+        y, slab = N.conv_fwd(nob, nhwc(x), stats=True, groups=G, tile=PATCH)
+    assert [(k, r.family, r.mtiles) for k, r in routes] == [("fwd", N.IGEMM_PATCH_F32, slab.shape[0])]
     raw = F.conv2d(x.double(), w.double(), None, padding=1)
     assert rel_err(nchw(y), raw) < 2e-6
     mt = slab.shape[0] // G
@@ -529,5 +564,7 @@ def test_fp32_patch_in_lds_kernel_matches_the_table_driven_one(case):
     aux = torch.randn(B, Cin, H, W, generator=g)
     add = torch.randn(B, Cin, H, W, generator=g)
     dxw = F.conv_transpose2d(dy.double(), w.double(), padding=1) * (aux.double() > 0) + add.double()
-    dx = N.conv_dgrad(spec, nhwc(dy), (H, W), dact_aux=nhwc(aux), dact=N.ACT_RELU, addend=nhwc(add), tile=PATCH)
+    with recorded_routes(N) as routes:
+        dx = N.conv_dgrad(spec, nhwc(dy), (H, W), dact_aux=nhwc(aux), dact=N.ACT_RELU, addend=nhwc(add), tile=PATCH)
+    assert [(k, r.family) for k, r in routes] == [("dgrad", N.IGEMM_PATCH_F32)]
     assert rel_err(nchw(dx), dxw) < 2e-6

@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_err
+from conv_plan_cases import recorded_routes
 from guarded import guard_allocations, guarded_spec
 from seeding import reinit_by_name
 from test_bf16_gpu import CASES, depth_of, ref_conv64
@@ -315,10 +316,16 @@ def test_second_patch_kernel_matches_float64_as_the_first_one_does(case, tile_bi
     errs = {}
     for name, tile in (("first", 0), ("second", tile_bits)):
         spec = spec_of(w, b, 1, 1, 0, N.MMA_SPLIT)
-        y = N.conv_fwd(spec, nhwc(x), act=N.ACT_RELU, tile=tile)
-        dx = N.conv_dgrad(spec, nhwc(dy), (H, W), tile=tile)
-        spec0 = spec_of(w, None, 1, 1, 0, N.MMA_SPLIT)
-        yraw, slab = N.conv_fwd(spec0, nhwc(x), stats=True, groups=2, tile=tile)
+        with recorded_routes(N) as routes:
+            y = N.conv_fwd(spec, nhwc(x), act=N.ACT_RELU, tile=tile)
+            dx = N.conv_dgrad(spec, nhwc(dy), (H, W), tile=tile)
+            spec0 = spec_of(w, None, 1, 1, 0, N.MMA_SPLIT)
+            yraw, slab = N.conv_fwd(spec0, nhwc(x), stats=True, groups=2, tile=tile)
+        assert [k for k, _ in routes] == ["fwd", "dgrad", "fwd"]
+        for kind, r in routes:                               # the planner's word for which kernel each launch took
+            assert r.family == (N.IGEMM_BF16_PATCH2 if tile else N.IGEMM_BF16_PATCH), (name, kind, r.family, r.variant)
+            assert r.variant & N.RV_SPLIT and bool(r.variant & N.RV_BN32) == bool(tile >> 15), (name, kind, r.variant)
+        assert routes[2][1].mtiles == slab.shape[0]
         mt = slab.shape[0] // 2
         s0 = torch.stack([slab[grp * mt:(grp + 1) * mt].double().sum(0).cpu() for grp in range(2)])      # [group][sum | sum of squares][channel]
         part = [raw[grp * (B // 2):(grp + 1) * (B // 2)] for grp in range(2)]
@@ -353,19 +360,27 @@ def test_twelve_wavefront_patch_kernel_matches_float64_as_the_first_one_does(cas
     errs = {}
     for name, tile in (("first", 0), ("twelve", 0x33)):
         spec = spec_of(w, b, 1, 1, pm, N.MMA_SPLIT_ALL)
-        y = N.conv_fwd(spec, nhwc(x), act=N.ACT_RELU, tile=tile)
-        dx = N.conv_dgrad(spec, nhwc(dy), (H, W), tile=tile)
+        with recorded_routes(N) as routes:
+            y = N.conv_fwd(spec, nhwc(x), act=N.ACT_RELU, tile=tile)
+            dx = N.conv_dgrad(spec, nhwc(dy), (H, W), tile=tile)
         e = [rel_err(nchw(y), want), rel_err(nchw(dx), xr.grad)]
         rows = 0
         if grouped:
             spec0 = spec_of(w, None, 1, 1, pm, N.MMA_SPLIT_ALL)
-            yraw, slab = N.conv_fwd(spec0, nhwc(x), stats=True, groups=2, tile=tile)
+            with recorded_routes(N) as stats_routes:
+                yraw, slab = N.conv_fwd(spec0, nhwc(x), stats=True, groups=2, tile=tile)
+            routes += stats_routes
+            assert stats_routes[0][1].mtiles == slab.shape[0]
             mt = slab.shape[0] // 2
             rows = slab.shape[0]
             s0 = torch.stack([slab[grp * mt:(grp + 1) * mt].double().sum(0).cpu() for grp in range(2)])
             part = [raw[grp * (B // 2):(grp + 1) * (B // 2)] for grp in range(2)]
             e += [rel_err(nchw(yraw), raw), max(rel_err(s0[grp][0], part[grp].sum((0, 2, 3))) for grp in range(2)),
                   max(rel_err(s0[grp][1], (part[grp] ** 2).sum((0, 2, 3))) for grp in range(2))]
+        assert [k for k, _ in routes] == ["fwd", "dgrad"] + ["fwd"] * grouped
+        for kind, r in routes:                               # the ungrouped cases too: the planner says which kernel each launch took
+            assert r.family == (N.IGEMM_BF16_PATCH3 if tile else N.IGEMM_BF16_PATCH), (name, kind, r.family, r.variant)
+            assert bool(r.variant & N.RV_ADJ) == (pm == 1 and kind == "dgrad") and bool(r.variant & N.RV_REFLECT) == (pm == 1), (name, kind, r.variant)
         errs[name] = (e, rows)
     print("patch kernels %s: first %s | twelve-wavefront %s" % (case, ["%.1e" % v for v in errs["first"][0]], ["%.1e" % v for v in errs["twelve"][0]]))
     if grouped:
@@ -429,8 +444,12 @@ def test_split_depth_stem_matches_float64_as_the_fp32_stem_kernel_does(B, H, W):
     for name, mma in (("fp32", N.MMA_FP32), ("split", N.MMA_SPLIT_ALL)):
         spec = N.ConvSpec(torch.nn.Parameter(w.to(DEV)), None, 2, 3, 0, smallc=True)
         spec.mma = mma
-        got, slab = N.conv_fwd(spec, x4, stats=True, groups=groups)
+        with recorded_routes(N) as routes:
+            got, slab = N.conv_fwd(spec, x4, stats=True, groups=groups)
         assert getattr(spec, "_stem", None) is not None
+        (kind, r), = routes
+        assert r.family == N.IGEMM_STEM and bool(r.variant & N.RV_SPLIT) == (mma == N.MMA_SPLIT_ALL) and not r.variant & N.RV_POSE, (name, r.family, r.variant)
+        assert r.mtiles == slab.shape[0]
         mt = slab.shape[0] // groups
         e = [rel_err(nchw(got), want), rms_err(nchw(got), want)]
         for grp in range(groups):

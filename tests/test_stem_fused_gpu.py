@@ -15,6 +15,7 @@ import pytest
 import torch
 
 from conftest import rel_err
+from conv_plan_cases import recorded_routes
 from guarded import guard_allocations
 
 pytestmark = pytest.mark.gpu
@@ -235,10 +236,12 @@ def test_stem_wide_store_epilogue_writes_the_lean_epilogues_bits(B, H, W):
     w = torch.randn(64, 3, 7, 7, generator=g) * 0.1 * torch.exp(1.5 * torch.randn(64, 1, 1, 1, generator=g))
     spec = N.ConvSpec(torch.nn.Parameter(w.to(DEV)), None, 2, 3, 0, smallc=True)
     x4 = N.nchw_to_nhwc(x.to(DEV), 4)
-    lean, slab_lean = N.conv_fwd(spec, x4, stats=True, groups=2, tile=STEM_LEAN)
-    wide, slab_wide = N.conv_fwd(spec, x4, stats=True, groups=2)
-    again, slab_again = N.conv_fwd(spec, x4, stats=True, groups=2)
-    plain = N.conv_fwd(spec, x4)                                                     # without statistics (eval mode)
+    with recorded_routes(N) as routes:
+        lean, slab_lean = N.conv_fwd(spec, x4, stats=True, groups=2, tile=STEM_LEAN)
+        wide, slab_wide = N.conv_fwd(spec, x4, stats=True, groups=2)
+        again, slab_again = N.conv_fwd(spec, x4, stats=True, groups=2)
+        plain = N.conv_fwd(spec, x4)                                                 # without statistics (eval mode)
+    assert [(k, r.family, r.variant) for k, r in routes] == [("fwd", N.IGEMM_STEM, N.RV_LEAN)] + [("fwd", N.IGEMM_STEM, 0)] * 3      # bit 16 forces the lean epilogue
     torch.cuda.synchronize()
     assert getattr(spec, "_stem", None) is not None, "the stem launch did not take the patch kernel"
     assert H % 2 == 0 or (wide.shape[1] % 8 and wide.shape[2] % 32), "the odd case has ragged tiles both ways"

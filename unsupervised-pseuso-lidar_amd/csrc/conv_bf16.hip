@@ -396,13 +396,6 @@ __device__ __forceinline__ int patch_pixel(int R) {
 // this ISA, and a patch-kernel workgroup of the 48x160 maps lives for only 6 stages.
 __device__ __forceinline__ int small_div(int n, float rcp_d) { return (int)(((float)n + 0.5f) * rcp_d); }
 
-struct PatchGeo {
-    int TH, TW, tiles_y, tiles_x;
-    int tmb;      // 32-row blocks per wavefront: 1 = 64-pixel blocks, 2 = 128-pixel blocks
-    int refl;     // 0 zero padding; 1 reflection padding, forward (the patch's ring is the mirrored row / column); 2 the ADJOINT of reflection
-                  // padding (the zero-padded data gradient plus the ring's contributions folded onto rows / columns 1 and H - 2 / W - 2)
-};
-
 // Timing experiments only, WRONG results: a compile-time value of experiment builds (make variant NAME=pd8 FLAGS=-DMCAV_PATCH_DIAG=8), zero
 // -- every branch on it folded away -- in the shipped library.  1 no filter staging in the loop, 2 no barriers, 4 no patch staging, 8 no
 // MFMAs, 16 no epilogue.
@@ -413,7 +406,7 @@ struct PatchGeo {
 template <int TMB>
 struct PatchCfg {                       // TMB 32-row blocks per wavefront: 64- or 128-pixel blocks
     static constexpr int BM = 64 * TMB;
-    static constexpr int PIX = TMB == 1 ? 110 : 180;      // patch pixels: (TH + 2)(TW + 2) <= PIX: 4 x 16 -> 108, 3 x 20 -> 110 (8 x 8 -> 100, 6 x 10 -> 96); 8 x 16 -> 180, 6 x 20 -> 176
+    static constexpr int PIX = patch_pix(TMB);            // patch pixels: (TH + 2)(TW + 2) <= PIX
     static constexpr int NJ = (PIX + 31) / 32;            // patch pixels staged per thread
     using T = typename std::conditional<TMB == 1, BT64x64k32, BT128x64k32>::type;
 };
@@ -710,7 +703,7 @@ struct P3Tile {
     static constexpr int BM = 192, BN = 64, MF = 32, ACC = 16, TM = 1, TN = 1, WAVES_M = 6, WAVES_N = 2;
     using AccT = f32x16;
 };
-constexpr int P3_THREADS = 768, P3_SUBS = 3, P3_PIX = 110;
+constexpr int P3_THREADS = 768;
 template <int NS> constexpr size_t patch3_lds_bytes() { return sizeof(u16) * (size_t)NS * (P3_SUBS * P3_PIX + 2 * 3 * 64) * 32 + sizeof(unsigned) * 192; }
 #ifndef MCAV_PATCH3_DIAG
 #define MCAV_PATCH3_DIAG 0
@@ -1385,135 +1378,11 @@ __global__ __launch_bounds__(256, TMB == 1 ? 4 : 3) void conv3x3_patch_f32_kerne
 template <int TMB>
 constexpr size_t patch_f32_lds_bytes() { return sizeof(float) * (size_t)(PatchCfg<TMB>::PIX + 3 * 64) * 32 + sizeof(unsigned) * 64 * TMB; }
 
-// The block shape for an H x W map: TH TW <= rows, (TH + 2)(TW + 2) <= pix, fewest wasted rows, then the smallest halo; 16-wide blocks read
-// the patch without bank conflicts (worth some wasted rows).  Returns the cost (rows computed, weighted).
-static double patch_block(int H, int W, int rows, int pix, int& TH, int& TW) {
-    double best = 1e30;
-    TH = 4; TW = 16;
-    for (int th = 1; th <= 16; ++th)
-        for (int tw = 4; tw <= 64; ++tw) {
-            if (th * tw > rows || (th + 2) * (tw + 2) > pix) continue;
-            const double tiles = (double)((H + th - 1) / th) * ((W + tw - 1) / tw);
-            // a lane group = 16 consecutive pixels of the block: one pixel row of a 16-wide block (conflict-free); of a wider block with
-            // tw % 4 == 0 at most two runs of a row each (two lanes collide); anything else scatters
-            const double bank = tw % 16 == 0 ? 1.0 : (tw > 16 && tw % 4 == 0 ? 1.05 : 1.25);
-            const double cost = tiles * rows * (1.0 + 0.05 * (double)((th + 2) * (tw + 2)) / (th * tw)) * bank;
-            if (cost < best) { best = cost; TH = th; TW = tw; }
-        }
-    return best;
-}
-
-// 1 = the descriptor runs on conv3x3_patch_kernel (fills geo): a 3x3 stride-1 zero-padded convolution or its data gradient, one source
-static bool patch_plan(const mcav_igemm_desc* d, PatchGeo& geo, bool f32 = false) {
-    static const int enabled = MCAV_KNOB_INT("MCAV_PATCH", 1);
-    if (!enabled || !d) return false;
-    if (f32 ? (d->mma != 0 || !d->w) : (!d->w16 || d->mma < 1 || d->mma > 3)) return false;
-    if (d->kh != 3 || d->kw != 3 || d->stride != 1) return false;
-    geo.refl = 0;
-    if (d->mode == MCAV_G_DIRECT && d->pad_mode == MCAV_PAD_REFLECT && d->sign == 1 && d->offset == -1) geo.refl = 1;
-    else if (d->mode == MCAV_G_ADJ_REFLECT && d->sign == -1 && d->offset == 1) geo.refl = 2;
-    else if (d->mode != MCAV_G_DIRECT || d->pad_mode != MCAV_PAD_ZERO) return false;
-    else if (!((d->sign == 1 && d->offset == -1) || (d->sign == -1 && d->offset == 1))) return false;
-    // reflection padding and its adjoint (the decoder's single-source 3x3 layers; round 4): the split form only
-    static const int refl_on = MCAV_KNOB_INT("MCAV_PATCH_REFLECT", 1);
-    if (geo.refl && (f32 || d->mma < 2 || !refl_on || d->Hs < 2 || d->Ws < 2)) return false;
-    // ... and where it was measured ahead of the fp32 kernels (batch 12, profiles/r04_reflect_patch.txt): 64 outputs or more (half of a 64-wide
-    // tile idle: 0.086 against 0.075 ms at 48x160, 64 -> 32), and for the adjoint the 24x80 maps and larger (12x40: level; 6x20, where every block
-    // is a border block and runs up to three times the MFMAs: 0.097 against 0.076 ms); mma = 3 (the parity tests) takes it on every shape
-    static const int refl_minpix = MCAV_KNOB_INT("MCAV_PATCH_REFLECT_MINPIX", 1000);
-    if (geo.refl && d->mma != 3 && (d->n_count < 64 || (geo.refl == 2 && d->Hd * d->Wd < refl_minpix))) return false;
-    if (d->C2 != 0 || d->up1 || d->pool || d->w_upmerge) return false;
-    if (d->C1 % 32 != 0 || d->Kp != d->C1 || d->Hd != d->Hs || d->Wd != d->Ws || d->n_count < 32) return false;
-    if (d->groups > 1 && d->B % d->groups != 0) return false;
-    // 128-pixel blocks (half the filter traffic per FLOP) where they waste no more rows than 64-pixel ones and still fill the chip
-    static const int force_tmb = MCAV_KNOB_INT("MCAV_PATCH_TMB", 0);
-    int th1, tw1, th2, tw2;
-    const double c1 = patch_block(d->Hd, d->Wd, 64, PatchCfg<1>::PIX, th1, tw1);
-    const double c2 = patch_block(d->Hd, d->Wd, 128, PatchCfg<2>::PIX, th2, tw2);
-    const long wg2 = (long)d->B * ((d->Hd + th2 - 1) / th2) * ((d->Wd + tw2 - 1) / tw2) * ((d->n_count + 63) / 64);
-    geo.tmb = (c2 <= c1 * 1.02 && wg2 >= 1024) ? 2 : 1;
-    if (force_tmb == 1 || force_tmb == 2) geo.tmb = force_tmb;
-    geo.TH = geo.tmb == 2 ? th2 : th1;
-    geo.TW = geo.tmb == 2 ? tw2 : tw1;
-    geo.tiles_y = (d->Hd + geo.TH - 1) / geo.TH;
-    geo.tiles_x = (d->Wd + geo.TW - 1) / geo.TW;
-    // plain bf16 on few blocks (the 6x20 maps): the table-driven 32x64 tiles are faster (0.043 against 0.055 ms on 512 -> 512)
-    if (d->mma == 1 && (long)d->B * geo.tiles_y * geo.tiles_x * ((d->n_count + 63) / 64) < 1024) return false;
-    return true;
-}
-
-// Twelve-wavefront form (conv3x3_patch3_kernel): three 64-pixel blocks per workgroup, one workgroup per CU.  The split form only; the three
-// blocks of a workgroup belong to one statistics group.  MCAV_PATCH3 (tune builds) / the low byte 0x33 of mcav_igemm_desc.tile (tests) select it.
-static int patch3_plan(const mcav_igemm_desc* d, PatchGeo& geo) {
-    static const int enabled = MCAV_KNOB_INT("MCAV_PATCH3", 0);       // OFF: ahead per launch on the 12x40 / 24x80 maps, level in the step (profiles/r04_patch3.txt)
-    static const int min_wgs = MCAV_KNOB_INT("MCAV_PATCH3_MIN_WGS", 192);
-    static const int min_k = MCAV_KNOB_INT("MCAV_PATCH3_MIN_K", 128);
-    if (!d || d->mma < 2) return 0;
-    const bool forced = (d->tile & 0xff) == 0x33;
-    if (!enabled && !forced) return 0;
-    PatchGeo g1;
-    if (!patch_plan(d, g1)) return 0;
-    int th, tw;
-    patch_block(d->Hd, d->Wd, 64, P3_PIX, th, tw);
-    geo = g1;
-    geo.TH = th; geo.TW = tw; geo.tmb = 1;
-    geo.tiles_y = (d->Hd + th - 1) / th;
-    geo.tiles_x = (d->Wd + tw - 1) / tw;
-    const long nblk = (long)d->B * geo.tiles_y * geo.tiles_x;
-    if (d->groups > 1 && (nblk / d->groups) % P3_SUBS != 0) return 0;
-    const long wgs = ((nblk + P3_SUBS - 1) / P3_SUBS) * ((d->n_count + 63) / 64);
-    // Where it was measured ahead of the first kernel (batch 12, profiles/r04_patch3.txt): 128 or more channels per tap (four or more chunks: a
-    // workgroup of two chunks lives for six stages and its set-up and epilogue run alone -- the 48x160 maps: 0.083 -> 0.096 ms) and enough
-    // workgroups for one per CU (the 6x20 maps give 128: 0.110 -> 0.117); the 12x40 / 24x80 trunk maps: 0.093 -> 0.079 / 0.085 ms.
-    if (!forced && (wgs < min_wgs || d->Kp < min_k)) return 0;
-    return 1;
-}
-
-// Second form (conv3x3_patch2_kernel): SB = 4 or 2 sub-blocks of 64 pixels per workgroup, one workgroup per CU; 0 = not this form.  The
-// choice is a count of rounds: a launch runs ceil(workgroups / CUs) rounds of SB units of work each, and the fewer sub-blocks win a tie only
-// when they save a round (the filter stream per FLOP doubles with them).  A workgroup's sub-blocks must belong to one statistics group.
-static int patch2_plan(const mcav_igemm_desc* d, PatchGeo& geo, int& bn) {
-    // OFF by default: measured level with or behind the first kernel on every trunk shape (profiles/r04_patch2_forms.txt).
-    // mcav_igemm_desc.tile bit 14 selects it (bit 15: its 128 x 32 two-workgroups-per-CU configuration): the parity tests; MCAV_PATCH2=1 in a
-    // -DMCAV_TUNE_ENV build: experiments.
-    static const int enabled = MCAV_KNOB_INT("MCAV_PATCH2", 0);
-    static const int force_sb = MCAV_KNOB_INT("MCAV_PATCH2_SB", 0);
-    static const int force_bn = MCAV_KNOB_INT("MCAV_PATCH2_BN", 0);
-    if (!d || d->mma < 2) return 0;                                   // (the split form; plain bf16 keeps the first kernel)
-    if (!enabled && !((d->tile >> 14) & 3)) return 0;
-    PatchGeo g1;
-    if (!patch_plan(d, g1) || g1.refl) return 0;                     // (reflection / its adjoint: the first kernel only)
-    int th, tw;
-    patch_block(d->Hd, d->Wd, 64, PatchCfg<1>::PIX, th, tw);
-    geo.TH = th; geo.TW = tw; geo.tmb = 1; geo.refl = 0;
-    geo.tiles_y = (d->Hd + th - 1) / th;
-    geo.tiles_x = (d->Wd + tw - 1) / tw;
-    const long per_img = (long)geo.tiles_y * geo.tiles_x, nblk = d->B * per_img, ntiles = (d->n_count + 63) / 64;
-    const int groups = (d->stats && d->groups > 1) ? d->groups : 1;
-    static const int cus = [] {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        const int n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-        (void)hipGetLastError();
-        return n;
-    }();
-    auto fits = [&](int sb) { return d->B % groups == 0 && ((d->B / groups) * per_img) % sb == 0; };
-    auto cost = [&](int sb) { const long wgs = ((nblk + sb - 1) / sb) * ntiles; return ((wgs + cus - 1) / cus) * sb; };
-    int sb = 0;
-    if (fits(4)) sb = 4;
-    if (fits(2) && (sb == 0 || cost(2) < cost(4))) sb = 2;
-    if ((force_sb == 2 || force_sb == 4) && fits(force_sb)) sb = force_sb;
-    bn = 64;
-    if ((force_bn == 32 || ((d->tile >> 15) & 1)) && fits(2)) { sb = 2; bn = 32; }
-    return sb;
-}
-
 // ------------------------------------------------------------------------------------------------ weight gradient
 // out[kflat, n] = sum_pix x(pix, tap)[c] * dy[pix, n] with both operands rounded to bf16 and the reduction over pixels on the MFMA's K axis.
 // K-tile = KPB = 64 pixels.  Threads 0..127 stage the A operand (x through the per-(pixel, tap) offset table), threads 128..255 the B
 // operand (dy rows): thread (col, pg) loads 4 channels (16 bytes) of the 8 consecutive pixels 8 pg .. 8 pg + 7 and writes, per channel, the
 // 8 pixels as one 16-byte LDS store into the k-contiguous panel row of that channel.
-constexpr int KPB = 64;
 
 __device__ __forceinline__ int wsw(int row, int kb) { return ((kb ^ ((row >> 1) & 7)) << 3); }      // element offset of k-block kb in a panel row
 
@@ -1782,209 +1651,68 @@ inline void launch_igemm_bf16(const IgemmParams& p, const void* w16, bool refl, 
     else timed_launch(igemm_bf16_kernel<T, 0, NS>, grid, dim3(256), tab_bytes, s, p, reinterpret_cast<const u16*>(w16));
 }
 
-// Which bf16 tile (0 = the launch is not one the bf16 kernels cover: the caller runs the fp32 path).  Sets *refl.
-static int bf16_tile_for(const mcav_igemm_desc* d, bool* refl) {
-    if (!d || !d->w16 || (d->mma < 1 || d->mma > 3)) return 0;
-    if (d->mma == 2) {
-        // The split form pays where the contraction dominates and the operands are converted once: the patch kernel.  On the table-driven
-        // kernels (a conversion per tap) it was measured level with or behind the fp32 MFMA kernels (mma = 3 runs those too: tests).
-        PatchGeo geo;
-        if (!patch_plan(d, geo)) return 0;
-    }
-    if (d->pool || d->w_upmerge) return 0;                            // pooled / merged-tap forms stay on the fp32 kernels
-    if (d->kh * d->kw > TAB_TAPS || d->Kp % 32 != 0 || d->C1 + d->C2 != d->Kp) return 0;
-    if ((d->C1 & 3) || (d->C2 & 3) || (d->C2 > 0 && d->C1 % 32 != 0)) return 0;
-    if (d->n_count < 32) return 0;                                    // narrow outputs: the halo / stencil kernels
-    if (d->C2 == 0 && d->C1 <= 32 && d->n_count <= 32 && d->kh == 3 && d->stride == 1) return 0;      // conv_halo.hip's shapes (mcav_try_halo runs first)
-    const bool direct = d->mode == MCAV_G_DIRECT || (d->mode == MCAV_G_ADJ_STRIDE2 && d->C2 == 0);
-    const bool radj = d->mode == MCAV_G_ADJ_REFLECT && d->C2 == 0;
-    if (!direct && !radj) return 0;
-    *refl = radj;
-    const bool k64 = d->mma == 1 && d->Kp % 64 == 0 && (d->C2 == 0 || d->C1 % 64 == 0);      // (the split form keeps 32-deep K-tiles: three planes per panel)
-    const long M = (long)d->B * d->Hd * d->Wd;
-    const long wg64 = ((M + 63) / 64) * ((d->n_count + 63) / 64);
-    int shape = 10;                                                   // 64 x 64
-    if (wg64 >= 4096 && !radj) shape = 8;                             // many rows: 128 x 64 (half the filter re-reads)
-    else if (wg64 < 512) shape = 12;                                  // few rows (6x20 maps): 32 x 64
-    if (d->mma >= 2) {
-        static const int forced = MCAV_KNOB_INT("MCAV_SPLIT_TILE", 0);      // tuning knob: 10 / 8 / 12
-        if ((forced == 10 || forced == 12 || (forced == 8 && !radj))) shape = forced;
-    }
-    return shape * 2 + (k64 ? 1 : 0);
-}
-
 }  // namespace mcav
 
 using namespace mcav;
 
-// fp32 MFMA patch kernel (mma = 0): which descriptors take it.  Measured level with the table-driven kernels on the 48x160 / 24x80 maps
-// (0.129 against 0.133 ms, 0.115 against 0.112) and behind them on the 12x40 / 6x20 maps (ragged 16-wide blocks), so it is OFF by default:
-// MCAV_PATCH_F32=1, or bit 13 of mcav_igemm_desc.tile (the parity test), selects it.
-static bool patch_f32_plan(const mcav_igemm_desc* d, PatchGeo& geo) {
-    static const int enabled = MCAV_KNOB_INT("MCAV_PATCH_F32", 0);
-    if (!d || (!enabled && !((d->tile >> 13) & 1))) return false;
-    return patch_plan(d, geo, true);
-}
-
-int mcav_patch_f32_mtiles(const mcav_igemm_desc* d) {
-    PatchGeo geo;
-    return patch_f32_plan(d, geo) ? d->B * geo.tiles_y * geo.tiles_x : 0;
-}
-
-bool mcav_try_patch_f32(const mcav_igemm_desc* d, hipStream_t s) {
-    PatchGeo geo;
-    if (!patch_f32_plan(d, geo)) return false;
-    mcav_igemm_desc dd = *d;
-    dd.tile = 2;
-    dd.w_upmerge = nullptr;
-    IgemmParams p;
-    int tile;
-    if (!fill_params(&dd, p, tile) || p.upm) return false;
-    p.mtiles = d->B * geo.tiles_y * geo.tiles_x;
-    p.ntiles = (p.n_count + 63) / 64;
+// mcav_igemm's fp32 patch family and its four bf16 families (plan_patch_f32 / plan_bf16, conv_plan.h): MCAV_OK / MCAV_E_*
+int mcav_patch_bf16_launch(const IgemmRoute& r, hipStream_t s) {
+    const IgemmParams& p = r.p;
+    const PatchGeo& geo = r.geo;
     const int grid = p.mtiles * p.ntiles;
-    if (geo.tmb == 2) timed_launch(conv3x3_patch_f32_kernel<2>, grid, dim3(256), patch_f32_lds_bytes<2>(), s, p, geo);
-    else timed_launch(conv3x3_patch_f32_kernel<1>, grid, dim3(256), patch_f32_lds_bytes<1>(), s, p, geo);
-    return true;
-}
-
-// returns 1 when the launch is not eligible (run the fp32 path), MCAV_OK / MCAV_E_* otherwise
-int mcav_bf16_igemm(const mcav_igemm_desc* d, hipStream_t s) {
-    bool refl = false;
-    const int bt = bf16_tile_for(d, &refl);
-    if (!bt) return 1;
-    mcav_igemm_desc dd = *d;
-    dd.tile = bt >> 1;                                                // the fp32 planner lays the rows out for these tile dimensions
-    dd.w_upmerge = nullptr;
-    IgemmParams p;
-    int tile;
-    // (past this point the caller may have put the bf16 copy into d->w as well: never fall through to the fp32 kernels)
- PatchGeo geo;
-    int bn2 = 64;
-    if (patch3_plan(d, geo)) {
-        dd.tile = 10;
-        if (!fill_params(&dd, p, tile) || p.upm) return MCAV_E_INVALID;
-        if ((long)d->Np * p.Kstride * 2 * 3 >= 0x7fffffffL) return MCAV_E_INVALID;
-        const long nblk = (long)d->B * geo.tiles_y * geo.tiles_x;
-        p.mtiles = (int)((nblk + P3_SUBS - 1) / P3_SUBS);            // rows of the statistics slab = workgroups (three blocks of one group each)
-        p.ntiles = (p.n_count + 63) / 64;
-        static const bool allowed = [] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_patch3_kernel<3, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)patch3_lds_bytes<3>()) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_patch3_kernel<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)patch3_lds_bytes<3>()) == hipSuccess;
-        }();
-        if (!allowed) return MCAV_E_LAUNCH;
-        const int grid = p.mtiles * p.ntiles;
-        const u16* w16 = reinterpret_cast<const u16*>(d->w16);
-        if (geo.refl == 2) timed_launch(conv3x3_patch3_kernel<3, true>, grid, dim3(P3_THREADS), patch3_lds_bytes<3>(), s, p, w16, geo);
-        else timed_launch(conv3x3_patch3_kernel<3, false>, grid, dim3(P3_THREADS), patch3_lds_bytes<3>(), s, p, w16, geo);
-        return launch_status();
-    }
-    if (const int sb = patch2_plan(d, geo, bn2)) {
-        dd.tile = 10;
-        if (!fill_params(&dd, p, tile) || p.upm) return MCAV_E_INVALID;
-        if ((long)d->Np * p.Kstride * 2 * 3 >= 0x7fffffffL) return MCAV_E_INVALID;
-        const long nblk = (long)d->B * geo.tiles_y * geo.tiles_x;
-        p.mtiles = (int)((nblk + sb - 1) / sb);                      // rows of the statistics slab = workgroup rows, image-major
-        p.ntiles = (p.n_count + bn2 - 1) / bn2;
-        static const bool allowed = [] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_patch2_kernel<3, 4, 64>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)patch2_lds_bytes<3, 4, 64>()) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_patch2_kernel<3, 2, 64>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)patch2_lds_bytes<3, 2, 64>()) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_patch2_kernel<3, 2, 32>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)patch2_lds_bytes<3, 2, 32>()) == hipSuccess;
-        }();
-        if (!allowed) return MCAV_E_LAUNCH;
-        const int grid = p.mtiles * p.ntiles;
-        const u16* w16 = reinterpret_cast<const u16*>(d->w16);
-        if (bn2 == 32) timed_launch(conv3x3_patch2_kernel<3, 2, 32>, grid, dim3(256), patch2_lds_bytes<3, 2, 32>(), s, p, w16, geo);
-        else if (sb == 4) timed_launch(conv3x3_patch2_kernel<3, 4, 64>, grid, dim3(256), patch2_lds_bytes<3, 4, 64>(), s, p, w16, geo);
-        else timed_launch(conv3x3_patch2_kernel<3, 2, 64>, grid, dim3(256), patch2_lds_bytes<3, 2, 64>(), s, p, w16, geo);
-        return launch_status();
-    }
-    if (patch_plan(d, geo)) {
-        dd.tile = 10;
-        if (!fill_params(&dd, p, tile) || p.upm) return MCAV_E_INVALID;
-        if ((long)d->Np * p.Kstride * 2 * (d->mma >= 2 ? 3 : 1) >= 0x7fffffffL) return MCAV_E_INVALID;
-        p.mtiles = d->B * geo.tiles_y * geo.tiles_x;                  // rows of the statistics slab = blocks, image-major (groups = runs of images)
-        p.ntiles = (p.n_count + 63) / 64;
-        // (more than 64 KB of dynamic LDS has to be allowed once per kernel)
-        static const bool allowed = [] {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_patch_kernel<3, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)patch_lds_bytes<3, 2>()) == hipSuccess &&
-                   hipFuncSetAttribute(reinterpret_cast<const void*>(conv3x3_patch_kernel<3, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)patch_lds_bytes<3, 2>()) == hipSuccess;
-        }();
-        const int grid = p.mtiles * p.ntiles;
-        const u16* w16 = reinterpret_cast<const u16*>(d->w16);
-        if (geo.refl == 2) {                                          // (patch_plan: the split form only)
-            if (geo.tmb == 2) {
-                if (!allowed) return MCAV_E_LAUNCH;
-                timed_launch(conv3x3_patch_kernel<3, 2, true>, grid, dim3(256), patch_lds_bytes<3, 2>(), s, p, w16, geo);
-            } else {
-                timed_launch(conv3x3_patch_kernel<3, 1, true>, grid, dim3(256), patch_lds_bytes<3, 1>(), s, p, w16, geo);
-            }
-        } else if (d->mma >= 2) {
-            if (geo.tmb == 2) {
-                if (!allowed) return MCAV_E_LAUNCH;
-                timed_launch(conv3x3_patch_kernel<3, 2>, grid, dim3(256), patch_lds_bytes<3, 2>(), s, p, w16, geo);
-            } else {
-                timed_launch(conv3x3_patch_kernel<3, 1>, grid, dim3(256), patch_lds_bytes<3, 1>(), s, p, w16, geo);
-            }
-        } else if (geo.tmb == 2) {
-            timed_launch(conv3x3_patch_kernel<1, 2>, grid, dim3(256), patch_lds_bytes<1, 2>(), s, p, w16, geo);
-        } else {
-            timed_launch(conv3x3_patch_kernel<1, 1>, grid, dim3(256), patch_lds_bytes<1, 1>(), s, p, w16, geo);
+    const u16* w16 = reinterpret_cast<const u16*>(r.d->w16);
+    const bool adj = r.variant & MCAV_RV_ADJ, split = r.variant & MCAV_RV_SPLIT, tmb2 = r.variant & MCAV_RV_TMB2, k64 = r.variant & MCAV_RV_K64;
+    switch (r.family) {
+        case MCAV_IGEMM_PATCH_F32:
+            if (tmb2) timed_launch(conv3x3_patch_f32_kernel<2>, grid, dim3(256), patch_f32_lds_bytes<2>(), s, p, geo);
+            else timed_launch(conv3x3_patch_f32_kernel<1>, grid, dim3(256), patch_f32_lds_bytes<1>(), s, p, geo);
+            break;
+        case MCAV_IGEMM_BF16_PATCH3: {
+            static const bool allowed = allow_dynamic_lds(patch3_lds_bytes<3>(), conv3x3_patch3_kernel<3, false>, conv3x3_patch3_kernel<3, true>);
+            if (!allowed) return MCAV_E_LAUNCH;
+            if (adj) timed_launch(conv3x3_patch3_kernel<3, true>, grid, dim3(P3_THREADS), patch3_lds_bytes<3>(), s, p, w16, geo);
+            else timed_launch(conv3x3_patch3_kernel<3, false>, grid, dim3(P3_THREADS), patch3_lds_bytes<3>(), s, p, w16, geo);
+            break;
         }
-        return launch_status();
-    }
-    if (!fill_params(&dd, p, tile) || p.upm) return MCAV_E_INVALID;
-    if ((long)d->Np * p.Kstride * 2 >= 0x7fffffffL) return MCAV_E_INVALID;
-    const bool k64 = bt & 1;
-    if (d->mma >= 2) {
-        if ((long)d->Np * p.Kstride * 2 * 3 >= 0x7fffffffL) return MCAV_E_INVALID;
-        switch (tile) {
-            case 10: launch_igemm_bf16<BT64x64k32, 3>(p, d->w16, refl, s); break;
-            case 8: launch_igemm_bf16<BT128x64k32, 3>(p, d->w16, refl, s); break;
-            case 12: launch_igemm_bf16<BT32x64k32, 3>(p, d->w16, refl, s); break;
-            default: return MCAV_E_INVALID;
+        case MCAV_IGEMM_BF16_PATCH2: {
+            static const bool allowed = allow_dynamic_lds(patch2_lds_bytes<3, 4, 64>(), conv3x3_patch2_kernel<3, 4, 64>) &&
+                                        allow_dynamic_lds(patch2_lds_bytes<3, 2, 64>(), conv3x3_patch2_kernel<3, 2, 64>) &&
+                                        allow_dynamic_lds(patch2_lds_bytes<3, 2, 32>(), conv3x3_patch2_kernel<3, 2, 32>);
+            if (!allowed) return MCAV_E_LAUNCH;
+            if (r.variant & MCAV_RV_BN32) timed_launch(conv3x3_patch2_kernel<3, 2, 32>, grid, dim3(256), patch2_lds_bytes<3, 2, 32>(), s, p, w16, geo);
+            else if (r.variant & MCAV_RV_SB4) timed_launch(conv3x3_patch2_kernel<3, 4, 64>, grid, dim3(256), patch2_lds_bytes<3, 4, 64>(), s, p, w16, geo);
+            else timed_launch(conv3x3_patch2_kernel<3, 2, 64>, grid, dim3(256), patch2_lds_bytes<3, 2, 64>(), s, p, w16, geo);
+            break;
         }
-        return launch_status();
-    }
-    switch (tile) {
-        case 10: if (k64) launch_igemm_bf16<BT64x64k64>(p, d->w16, refl, s); else launch_igemm_bf16<BT64x64k32>(p, d->w16, refl, s); break;
-        case 8: if (k64) launch_igemm_bf16<BT128x64k64>(p, d->w16, refl, s); else launch_igemm_bf16<BT128x64k32>(p, d->w16, refl, s); break;
-        case 12: if (k64) launch_igemm_bf16<BT32x64k64>(p, d->w16, refl, s); else launch_igemm_bf16<BT32x64k32>(p, d->w16, refl, s); break;
+        case MCAV_IGEMM_BF16_PATCH: {
+            // (only the 128-pixel blocks of the split form need more than 64 KB)
+            static const bool allowed = allow_dynamic_lds(patch_lds_bytes<3, 2>(), conv3x3_patch_kernel<3, 2>, conv3x3_patch_kernel<3, 2, true>);
+            if (split && tmb2 && !allowed) return MCAV_E_LAUNCH;
+            if (adj && tmb2) timed_launch(conv3x3_patch_kernel<3, 2, true>, grid, dim3(256), patch_lds_bytes<3, 2>(), s, p, w16, geo);      // (patch_plan: the split form only)
+            else if (adj) timed_launch(conv3x3_patch_kernel<3, 1, true>, grid, dim3(256), patch_lds_bytes<3, 1>(), s, p, w16, geo);
+            else if (split && tmb2) timed_launch(conv3x3_patch_kernel<3, 2>, grid, dim3(256), patch_lds_bytes<3, 2>(), s, p, w16, geo);
+            else if (split) timed_launch(conv3x3_patch_kernel<3, 1>, grid, dim3(256), patch_lds_bytes<3, 1>(), s, p, w16, geo);
+            else if (tmb2) timed_launch(conv3x3_patch_kernel<1, 2>, grid, dim3(256), patch_lds_bytes<1, 2>(), s, p, w16, geo);
+            else timed_launch(conv3x3_patch_kernel<1, 1>, grid, dim3(256), patch_lds_bytes<1, 1>(), s, p, w16, geo);
+            break;
+        }
+        case MCAV_IGEMM_BF16_TILE:
+            switch (r.tile * 4 + (split ? 2 : 0) + (k64 ? 1 : 0)) {
+                case 10 * 4 + 2: launch_igemm_bf16<BT64x64k32, 3>(p, w16, adj, s); break;
+                case 8 * 4 + 2: launch_igemm_bf16<BT128x64k32, 3>(p, w16, adj, s); break;
+                case 12 * 4 + 2: launch_igemm_bf16<BT32x64k32, 3>(p, w16, adj, s); break;
+                case 10 * 4 + 1: launch_igemm_bf16<BT64x64k64>(p, w16, adj, s); break;
+                case 10 * 4: launch_igemm_bf16<BT64x64k32>(p, w16, adj, s); break;
+                case 8 * 4 + 1: launch_igemm_bf16<BT128x64k64>(p, w16, adj, s); break;
+                case 8 * 4: launch_igemm_bf16<BT128x64k32>(p, w16, adj, s); break;
+                case 12 * 4 + 1: launch_igemm_bf16<BT32x64k64>(p, w16, adj, s); break;
+                case 12 * 4: launch_igemm_bf16<BT32x64k32>(p, w16, adj, s); break;
+                default: return MCAV_E_INVALID;
+            }
+            break;
         default: return MCAV_E_INVALID;
     }
     return launch_status();
-}
-
-// The M-tile count (rows of the BatchNorm statistics slab) of the bf16 launch, whose tile shape is chosen independently of the fp32
-// planner's: 0 when the descriptor does not run on the bf16 kernels.
-int mcav_bf16_igemm_mtiles(const mcav_igemm_desc* d) {
-    bool refl = false;
-    const int bt = bf16_tile_for(d, &refl);
-    if (!bt) return 0;
-    PatchGeo geo;
-    int bn2 = 64;
-    if (patch3_plan(d, geo)) return (int)(((long)d->B * geo.tiles_y * geo.tiles_x + P3_SUBS - 1) / P3_SUBS);
-    if (const int sb = patch2_plan(d, geo, bn2)) return (int)(((long)d->B * geo.tiles_y * geo.tiles_x + sb - 1) / sb);
-    if (patch_plan(d, geo)) return d->B * geo.tiles_y * geo.tiles_x;
-    mcav_igemm_desc dd = *d;
-    dd.tile = bt >> 1;
-    dd.w_upmerge = nullptr;
-    IgemmParams p;
-    int tile;
-    if (!fill_params(&dd, p, tile) || p.upm) return 0;
-    return p.mtiles;
-}
-
-MCAV_EXPORT int mcav_igemm_uses_bf16(const mcav_igemm_desc* d) {
-    bool refl = false;
-    return bf16_tile_for(d, &refl) != 0;
 }
 
 // ------------------------------------------------------------------------------------------------ weight gradient on the patch (round 4)
@@ -2003,7 +1731,6 @@ MCAV_EXPORT int mcav_igemm_uses_bf16(const mcav_igemm_desc* d) {
 // batched presum / reduce launches in the same fixed order.
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-constexpr int WGP_PIX = 110;                       // patch pixels (PatchCfg<1>::PIX)
 constexpr int WGP_THREADS = 768;
 template <int NS> struct WgpCfg {                  // NS planes per operand: 3 = the split fp32 form, 1 = plain bf16 (mcav_wgrad_desc.mma = 1)
     static constexpr int XS = NS * WGP_PIX * 32;   // u16 elements: one 32-channel half of the patch
@@ -2266,103 +1993,6 @@ __global__ __launch_bounds__(WGP_THREADS, 1) void wgrad3x3_patch_kernel(WgradPar
     }
 }
 
-// Which weight gradients take wgrad3x3_patch_kernel: 3x3 stride 1, zero or reflection padding, one source of 64-channel multiples, >= 64 outputs.
-static bool wgrad_patch_plan(const mcav_wgrad_desc* d, WgradPlan& pl) {
-    static const int enabled = MCAV_KNOB_INT("MCAV_WGRAD_PATCH", 1);
-    static const int target = MCAV_KNOB_INT("MCAV_WGRAD_PATCH_WGS", 256);
-    if (!enabled || !d || d->mma < 1 || d->mma > 3 || d->upm || d->up1 || d->C2 != 0) return false;
-    if (d->mode != MCAV_G_DIRECT || d->kh != 3 || d->kw != 3 || d->stride != 1 || d->sign != 1 || d->offset != -1) return false;
-    if (d->pad_mode != MCAV_PAD_ZERO && d->pad_mode != MCAV_PAD_REFLECT) return false;
-    if (d->pad_mode == MCAV_PAD_REFLECT && (d->Hs < 2 || d->Ws < 2)) return false;
-    if (d->C1 != d->Kp || d->Cin != d->Kp || d->Kp % 64 != 0 || d->Cout < 32 || d->Hd != d->Hs || d->Wd != d->Ws) return false;
-    if (d->Cout < 64 && d->Cout != 32) return false;                  // (32 outputs: the narrow form; 33 .. 63 would leave half of a 64-wide tile idle)
-    if ((d->Cdy & 3) || (d->dy_choff & 3)) return false;
-    mcav_wgrad_desc dd = *d;
-    dd.tile = 2;
-    if (!plan_wgrad(&dd, pl) || pl.use_halo || pl.use_stem) return false;
-    WgradParams& p = pl.p;
-    if ((p.CoutLoad & 3) != 0) return false;
-    int th, tw;
-    patch_block(d->Hd, d->Wd, 64, WGP_PIX, th, tw);
-    p.patch = 1; p.split_planes = d->mma >= 2;
-    p.pTH = th; p.pTW = tw;
-    p.ptiles_y = (d->Hd + th - 1) / th; p.ptiles_x = (d->Wd + tw - 1) / tw;
-    p.prefl = d->pad_mode == MCAV_PAD_REFLECT;
-    p.pnblocks = d->B * p.ptiles_y * p.ptiles_x;
-    p.pct_co = (d->Cout + 63) / 64;
-    p.pnarrow = d->Cout <= 32;
-    const int ctiles = (d->Kp / 64) * p.pct_co;
-    int splits = target / ctiles;                                     // one workgroup per CU
-    if (splits < 1) splits = 1;
-    if (splits > p.pnblocks) splits = p.pnblocks;
-    p.pbps = (p.pnblocks + splits - 1) / splits;
-    p.splits = (p.pnblocks + p.pbps - 1) / p.pbps * (p.pnarrow ? 2 : 1);      // slab splits
-    pl.use_tab = false;
-    pl.slab_bytes = align_up(sizeof(float) * (size_t)p.splits * (p.Ktot + 1) * p.slabN, 256);
-    pl.groups = p.splits > 8 ? 8 : 0;
-    pl.per_group = pl.groups ? (p.splits + pl.groups - 1) / pl.groups : 0;
-    if (pl.groups) pl.groups = (p.splits + pl.per_group - 1) / pl.per_group;
-    pl.pre_bytes = align_up(sizeof(float) * (size_t)pl.groups * (p.Ktot + 1) * p.slabN, 256);
-    return true;
-}
-
-// Plans the bf16 weight-gradient launch into pl (splits over 64-pixel K-tiles, table chunking); false = not eligible.
-bool mcav_bf16_wgrad_plan(const mcav_wgrad_desc* d, WgradPlan& pl) {
-    if (!d || (d->mma < 1 || d->mma > 3) || d->upm) return false;
-    if (wgrad_patch_plan(d, pl)) return true;
-    if (d->mma == 2) return false;                                    // mma = 2: the split form where it is ahead (the patch kernel), else fp32 MFMA
-    if (d->mode != MCAV_G_DIRECT || d->Kp % 16 != 0 || d->C1 + d->C2 != d->Kp || d->Cin != d->Kp) return false;
-    if ((d->C1 & 15) || (d->C2 & 15) || d->Cout < 32 || (d->Cdy & 3) || (d->dy_choff & 3)) return false;
-    mcav_wgrad_desc dd = *d;
-    dd.tile = 2;                                                      // 64 x 64 slab tiles
-    if (!plan_wgrad(&dd, pl) || pl.use_halo) return false;
-    WgradParams& p = pl.p;
-    if ((p.CoutLoad & 3) != 0) return false;
-    const int out_tiles = p.mtiles * p.ntiles;
-    // whole generations of the 1024 resident workgroups (four per CU), as plan_wgrad does: the fewest splits whose last generation is 95 % full
-    int max_splits = (p.Mpix + 4 * KPB - 1) / (4 * KPB);
-    if (max_splits > 512) max_splits = 512;
-    if (max_splits < 1) max_splits = 1;
-    const int slots = 1024;
-    auto pps_of = [&](int sp) { return ((p.Mpix + sp - 1) / sp + KPB - 1) / KPB * KPB; };
-    int lo = slots / out_tiles, hi = 3 * slots / out_tiles + 1;
-    if (lo < 1) lo = 1;
-    if (lo > max_splits) lo = max_splits;
-    if (hi > max_splits) hi = max_splits;
-    int splits = lo;
-    double best = -1.0;
-    for (int sp = lo; sp <= hi; ++sp) {
-        const int w = out_tiles * ((p.Mpix + pps_of(sp) - 1) / pps_of(sp)), gens = (w + slots - 1) / slots;
-        const double fill = (double)w / ((double)gens * slots);
-        if (fill > best + 1e-9) { best = fill; splits = sp; }
-        if (fill >= 0.95) { splits = sp; break; }
-    }
-    p.pix_per_split = pps_of(splits);
-    p.splits = (p.Mpix + p.pix_per_split - 1) / p.pix_per_split;
-    int ntmax = 1;
-    for (int mt = 0; mt < p.mtiles; ++mt) {
-        const int lo = mt * 64 / d->Kp, hi = (mt * 64 + 63) / d->Kp < p.taps - 1 ? (mt * 64 + 63) / d->Kp : p.taps - 1;
-        if (hi - lo + 1 > ntmax) ntmax = hi - lo + 1;
-    }
-    const int epp = ntmax * (d->C2 > 0 ? 2 : 1);
-    p.tab_cht_log2 = 20;
-    const int tabcap = d->mma >= 2 ? WG_TABCAP / 2 : WG_TABCAP;       // (the split form gives half of the table's LDS to its planes)
-    if ((long)p.pix_per_split * epp > tabcap) {
-        if (2 * 2 * KPB * epp > tabcap) return false;                 // not even two 2-tile chunks fit
-        int lg = 1;
-        while ((2 << lg) * KPB * epp <= tabcap / 2) ++lg;
-        p.tab_cht_log2 = lg;
-    }
-    p.split_planes = d->mma >= 2;
-    pl.use_tab = true;
-    pl.slab_bytes = align_up(sizeof(float) * (size_t)p.splits * (p.Ktot + 1) * p.slabN, 256);
-    pl.groups = p.splits > 8 ? 8 : 0;
-    pl.per_group = pl.groups ? (p.splits + pl.groups - 1) / pl.groups : 0;
-    if (pl.groups) pl.groups = (p.splits + pl.per_group - 1) / pl.per_group;
-    pl.pre_bytes = align_up(sizeof(float) * (size_t)pl.groups * (p.Ktot + 1) * p.slabN, 256);
-    return true;
-}
-
 namespace mcav {
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, size_t n) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) dst[i] = (__bf16)src[i];
@@ -2401,14 +2031,8 @@ MCAV_EXPORT int mcav_f32_to_bf16(const float* src, void* dst_bf16, size_t n, voi
 
 void mcav_bf16_wgrad_launch(const WgradParams& p, hipStream_t s) {
     if (p.patch) {
-        static const bool allowed = [] {
-            bool ok = true;
-            ok &= hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3x3_patch_kernel<3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wgrad_patch_lds_bytes<3>()) == hipSuccess;
-            ok &= hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3x3_patch_kernel<3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wgrad_patch_lds_bytes<3>()) == hipSuccess;
-            ok &= hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3x3_patch_kernel<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wgrad_patch_lds_bytes<1>()) == hipSuccess;
-            ok &= hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad3x3_patch_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wgrad_patch_lds_bytes<1>()) == hipSuccess;
-            return ok;
-        }();
+        static const bool allowed = allow_dynamic_lds(wgrad_patch_lds_bytes<3>(), wgrad3x3_patch_kernel<3, false>, wgrad3x3_patch_kernel<3, true>) &&
+                                    allow_dynamic_lds(wgrad_patch_lds_bytes<1>(), wgrad3x3_patch_kernel<1, false>, wgrad3x3_patch_kernel<1, true>);
         (void)allowed;                                                // (refused: the launch itself fails and launch_status() reports it)
         const int grid = (p.pnarrow ? p.splits / 2 : p.splits) * (p.Kp / 64) * p.pct_co;
         if (p.split_planes) {

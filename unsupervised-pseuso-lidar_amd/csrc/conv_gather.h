@@ -3,22 +3,14 @@
 // padding, the fused nearest-upsample + channel-concat of the decoder, and the two adjoint gathers.
 #pragma once
 #include "mcav_common.h"
-#include "../../include/mcav_conv.h"
+#include "conv_plan.h"      // the plain parameter blocks (GatherSrc, IgemmParams, ...) and the sizes the host planner shares with the kernels
 
 namespace mcav {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int CK = 16;         // K-tile depth: 16 input channels of one filter tap
 constexpr int LDK = CK + 4;    // LDS row stride (floats) of a [rows][CK] operand tile: conflict-free ds_read_b128
-
-struct GatherSrc {
-    const float* x1;
-    const float* x2;
-    int B, Hs, Ws, C1, C2, up1;
-    int mode, stride, sign, offset, pad_mode;
-};
 
 __device__ __forceinline__ int reflect_idx(int i, int n) {
     i = i < 0 ? -i : i;
@@ -96,33 +88,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 // ------------------------------------------------------------------------------------------------ shared by the conv kernels
-struct IgemmParams {
-    GatherSrc g;
-    const float* w;
-    int kh, kw, Kp, Kstride, taps;
-    float* y;
-    int Hd, Wd, Cd, n_begin, n_count, y_choff;
-    const float* bias;
-    int act;
-    const float* dact_aux;
-    int dact;
-    const float* addend;
-    int pool;
-    float* stats;
-    const float *stats_x, *stats_mean, *stats_invstd;      // BatchNorm-backward form of the statistics (mcav_igemm_desc.stats_x)
-    int M;           // rows of the GEMM (incl. class / group padding)
-    int Mc, McP;     // ADJ_STRIDE2: pixels per parity class and its BM-padded size; groups > 1: rows per group and padded size
-    int groups;
-    int mtiles, ntiles;
-    int no_tab;      // desc.tile bit 8: force the general kernel (A/B timing and parity of both paths)
-    const float* wm; // merged-tap filter copy (mcav_pack_weights_upmerge)
-    int Np_all;      // packed filter rows (desc.Np)
-    int bm;          // rows per tile of the chosen config (UPM row order: tiles of the four classes of one region are adjacent)
-    int upm;         // 1: rows are grouped by output parity class and the x1 part of K runs as 4 merged taps on the low-resolution source
-    int ksplit;      // > 1: the K loop of a tile is cut into ksplit workgroups (launches of a handful of tiles: PoseNet's 2x5 .. 6x20 maps);
-    float* kslab;    //      each writes its raw partial tile to kslab[split] (y-shaped), splitk_finish_kernel sums them and applies the epilogue
-};
-
 __device__ __forceinline__ float act_fwd(float v, int act) {
     if (act == MCAV_ACT_RELU) return v > 0.f ? v : 0.f;
     if (act == MCAV_ACT_ELU) return v > 0.f ? v : expm1f(v);

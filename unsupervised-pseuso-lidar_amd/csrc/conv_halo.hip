@@ -15,7 +15,6 @@
 
 namespace mcav {
 
-constexpr int HT_H = 8, HT_W = 32;                  // output tile
 constexpr int HH = HT_H + 2, HW = HT_W + 2;         // halo
 
 struct HaloParams {
@@ -679,25 +678,11 @@ __global__ __launch_bounds__(256) void conv3x3_halo_wgrad_up_kernel(HaloWgradPar
 
 using namespace mcav;
 
-// Called by mcav_igemm (conv_igemm.hip) for the shapes these kernels cover; returns false when they do not apply.
-bool mcav_try_halo(const mcav_igemm_desc* d, hipStream_t s) {
-    if (d->kh != 3 || d->kw != 3 || d->stride != 1) return false;
-    if (d->C2 != 0 || d->x2 || (d->C1 != 16 && d->C1 != 32) || d->Kp != d->C1) return false;
-    if (d->n_count > 32 || d->stats || d->groups > 1 || d->y_choff != 0) return false;      // wider outputs: the table-driven kernel is faster
-    if (d->Hd != d->Hs || d->Wd != d->Ws || d->Hs < 2 || d->Ws < 2) return false;
-    if ((d->tile >> 9) & 1) return false;                      // desc.tile bit 9: force the general kernels (A/B timing, parity of both)
-    const bool adj = d->mode == MCAV_G_ADJ_REFLECT;
-    if (adj) {
-        if (d->dact & ~0xff) return false;                     // MCAV_DACT_AFTER_ADDEND and any later flag: the table-driven kernel's epilogue honours them, this one applies act' first
-        if (d->up1 || d->bias || d->act != MCAV_ACT_NONE) return false;
-        if (d->pool && ((d->Hs & 1) || (d->Ws & 1))) return false;
-    } else {
-        if (d->mode != MCAV_G_DIRECT || d->sign != 1 || d->offset != -1) return false;
-        if (d->n_begin != 0 || d->pool || d->dact_aux || d->addend) return false;
-    }
-    // 32 input channels x 32 output channels would hold 144 filter registers per lane (one wavefront per SIMD): two launches of 16
-    const int nf = (d->n_count > 16 && d->C1 == 16) ? 2 : 1;
-    if (d->n_begin + (d->n_count + 15) / 16 * 16 > d->Np) return false;            // every filter row a launch touches exists in the packed copy
+// mcav_igemm's halo family (plan_halo, conv_plan.h)
+void mcav_halo_launch(const IgemmRoute& r, hipStream_t s) {
+    const mcav_igemm_desc* d = r.d;
+    const bool adj = r.variant & MCAV_RV_ADJ;
+    const int nf = (d->n_count > 16 && d->C1 == 16) ? 2 : 1;      // filter blocks of 16 outputs per launch (plan_halo)
     HaloParams p;
     p.x = d->x1; p.B = d->B; p.H = d->Hs; p.W = d->Ws; p.up = d->up1; p.pad_mode = d->pad_mode;
     p.w = d->w; p.n_begin = d->n_begin; p.bias = d->bias; p.act = d->act; p.y = d->y; p.Cd = d->Cd; p.n_count = d->n_count;
@@ -706,45 +691,29 @@ bool mcav_try_halo(const mcav_igemm_desc* d, hipStream_t s) {
     const int grid = p.B * p.tiles_x * p.tiles_y;
 #define HALO_LAUNCH(CC, NN) \
     do { if (adj) timed_launch(conv3x3_halo_kernel<CC, NN, true>, grid, dim3(256), 0, s, p); else timed_launch(conv3x3_halo_kernel<CC, NN, false>, grid, dim3(256), 0, s, p); } while (0)
-    // upsampled source + reflection padding: 4 merged taps on the low-resolution map (desc.tile bit 10 keeps the 9-tap kernel)
-    if (!adj && d->up1 && d->pad_mode == MCAV_PAD_REFLECT && !(d->Hs & 1) && !(d->Ws & 1) && !((d->tile >> 10) & 1)) {
-        for (p.co0 = 0; p.co0 < d->n_count; p.co0 += 16 * nf) {
+    for (p.co0 = 0; p.co0 < d->n_count; p.co0 += 16 * nf) {
+        if (r.variant & MCAV_RV_UPM) {                        // 4 merged taps on the low-resolution map
             if (d->C1 == 16 && nf == 1) timed_launch(conv3x3_halo_up_kernel<16, 1>, grid, dim3(256), 0, s, p);
             else if (d->C1 == 16) timed_launch(conv3x3_halo_up_kernel<16, 2>, grid, dim3(256), 0, s, p);
             else timed_launch(conv3x3_halo_up_kernel<32, 1>, grid, dim3(256), 0, s, p);
         }
-        return true;
-    }
-    for (p.co0 = 0; p.co0 < d->n_count; p.co0 += 16 * nf) {
-        if (d->C1 == 16 && nf == 1) HALO_LAUNCH(16, 1);
+        else if (d->C1 == 16 && nf == 1) HALO_LAUNCH(16, 1);
         else if (d->C1 == 16) HALO_LAUNCH(16, 2);
         else HALO_LAUNCH(32, 1);
     }
 #undef HALO_LAUNCH
-    return true;
 }
 
-// Weight-gradient counterpart (called by mcav_wgrad's planner / launcher in conv_igemm.hip).
-int mcav_halo_wgrad_splits(const mcav_wgrad_desc* d) {      // 0 = not applicable, else the number of slab partials (= workgroups)
-    if (d->mode != MCAV_G_DIRECT || d->kh != 3 || d->kw != 3 || d->stride != 1 || d->sign != 1 || d->offset != -1) return 0;
-    if (d->C2 != 0 || d->x2 || (d->C1 != 16 && d->C1 != 32) || d->Kp != d->C1 || d->Cin != d->C1) return 0;
-    if (d->Cout > 32 || (d->C1 == 32 && d->Cout > 16)) return 0;
-    if (d->Hd != d->Hs || d->Wd != d->Ws || d->Hs < 2 || d->Ws < 2) return 0;
-    if ((d->Cdy & 3) || (d->dy_choff & 3) || ((d->tile >> 9) & 1)) return 0;
-    const int cl = (d->Cout + 3) / 4 * 4;
-    if (cl > d->Cdy - d->dy_choff) return 0;                 // the 16-byte dy loads need the (zero) padding channels to exist
-    const long tiles = (long)d->B * ((d->Hs + HT_H - 1) / HT_H) * ((d->Ws + HT_W - 1) / HT_W);
-    return (int)(tiles < 512 ? tiles : 512);
-}
-
-void mcav_halo_wgrad_launch(const mcav_wgrad_desc* d, float* slab, int slabN, int splits, hipStream_t s) {
+// mcav_wgrad's halo family (halo_wgrad_splits, conv_plan.h): writes the slab partials
+void mcav_halo_wgrad_launch(const WgradRoute& r, hipStream_t s) {
+    const mcav_wgrad_desc* d = r.d;
+    const int splits = r.pl.p.splits;
     HaloWgradParams p;
     p.x = d->x1; p.B = d->B; p.H = d->Hs; p.W = d->Ws; p.up = d->up1; p.pad_mode = d->pad_mode;
     p.dy = d->dy; p.Cdy = d->Cdy; p.dy_choff = d->dy_choff; p.Cout = d->Cout;
-    p.slab = slab; p.slabN = slabN; p.Ktot = 9 * d->Kp; p.want_bias = d->dbias != nullptr;
+    p.slab = r.pl.p.slab; p.slabN = r.pl.p.slabN; p.Ktot = 9 * d->Kp; p.want_bias = d->dbias != nullptr;
     p.tiles_x = (p.W + HT_W - 1) / HT_W; p.tiles_y = (p.H + HT_H - 1) / HT_H; p.tiles = p.B * p.tiles_x * p.tiles_y;
-    if (p.up && p.pad_mode == MCAV_PAD_REFLECT && !(p.H & 1) && !(p.W & 1) && d->C1 == 16 && d->Cout <= 16 && !((d->tile >> 10) & 1))
-        timed_launch(conv3x3_halo_wgrad_up_kernel<16, 1>, dim3(splits), dim3(256), 0, s, p);
+    if (r.variant & MCAV_RV_UPM) timed_launch(conv3x3_halo_wgrad_up_kernel<16, 1>, dim3(splits), dim3(256), 0, s, p);
     else if (d->C1 == 16 && d->Cout <= 16) timed_launch(conv3x3_halo_wgrad_kernel<16, 1>, dim3(splits), dim3(256), 0, s, p);
     else if (d->C1 == 16) timed_launch(conv3x3_halo_wgrad_kernel<16, 2>, dim3(splits), dim3(256), 0, s, p);
     else timed_launch(conv3x3_halo_wgrad_kernel<32, 1>, dim3(splits), dim3(256), 0, s, p);

@@ -1764,132 +1764,6 @@ __global__ __launch_bounds__(256) void pack_weights_multi_kernel(const PackItem*
     }
 }
 
-inline int round_up(int v, int a) { return (v + a - 1) / a * a; }
-
-inline int kstride_of(int taps, int Kp) { return round_up(taps * Kp, CK); }
-
-inline int pick_tile(const mcav_igemm_desc* d, long M) {
-    if (d->tile) return d->tile;
-    if (d->n_count <= 16) return (M >= 256 * 64 && d->kh * d->kw <= 16) ? 4 : 6;      // (a 25-tap table for 256 rows is 26 KB of LDS: 64x16 tiles, 0.071 -> 0.051 ms)
-    // 32 output channels: 128x32 tiles (31 KB of LDS with the table, five workgroups per CU) beat 256x32 (56-60 KB, two) on every such
-    // launch of the step: 96->32 @96x320 merged-tap forward 0.333 -> 0.289 ms, its pooled adjoint 0.089 -> 0.071, 64->32 @48x160 0.081 -> 0.070
-    if (d->n_count <= 32) return 7;
-    // The reflection-adjoint kind carries three extra register stages for its border loads: on the 128-row tiles that is 122 VGPRs and two
-    // workgroups per CU.  Measured (MI355X, bench.py --layer-report, 96x320 / 48x160 maps): 128x64 0.370 / 0.129 / 0.181 ms, 64x64x32
-    // 0.331 / 0.113 / 0.159, 64x64x16 0.300 / 0.100 / 0.154 -- the small maps keep the choices below.  (Re-measured with the reflected sources
-    // in tables: 64x64x16 0.265 / 0.078 / 0.131, 128x64 0.274 / 0.080 / 0.134, 64x64x32 0.292 / 0.085 / 0.138.)
-    if (d->mode == MCAV_G_ADJ_REFLECT && ((M + 127) / 128) * ((d->n_count + 63) / 64) >= 1024) return 2;
-    // measured on MI355X (tools/conv_bench.py): small output tiles with 32-deep K-tiles win at every layer shape of the step --
-    // more co-resident workgroups hide the load round trips, and a 32-deep tile halves the barriers per FLOP
-    if (d->mode != MCAV_G_SMALLC && ((M + 127) / 128) * ((d->n_count + 63) / 64) >= 1024) return 1;   // many rows (layer1, 48x160): 128x64 tiles, 104 vs 96 TF/s
-    // few 64x64 workgroups (layer4's 6x20 maps, M = 2880): 32x64 tiles double them -- 84 -> 104 TF/s on 512->512
-    // ... when halving the tiles shortens the longest CU's queue: up to 128 tiles (each half on a CU of its own) or 257..511 (two halves
-    // balance better than one whole); in between the halves only pair up on the same CUs (6x20 512->256, 180 tiles: 74 TF/s halved, 87 whole)
-    const long t64 = ((M + 63) / 64) * ((d->n_count + 63) / 64);
-    if (d->mode != MCAV_G_SMALLC && d->Kp % 32 == 0 && (t64 <= 128 || (t64 > 256 && t64 < 512))) return 12;
-    if (d->mode != MCAV_G_SMALLC && d->Kp % 32 == 0) return 10;
-    const long t128x64 = ((M + 127) / 128) * ((d->n_count + 63) / 64);
-    return t128x64 >= 1024 ? 1 : 2;
-}
-
-void tile_dims(int id, int& BM, int& BN) {
-    switch (id) {
-        case 1: BM = 128; BN = 64; break;
-        case 2: BM = 64; BN = 64; break;
-        case 3: BM = 256; BN = 32; break;
-        case 4: BM = 256; BN = 16; break;
-        case 5: BM = 128; BN = 128; break;
-        case 7: BM = 128; BN = 32; break;
-        case 8: BM = 128; BN = 64; break;
-        case 9: BM = 128; BN = 128; break;
-        case 10: BM = 64; BN = 64; break;
-        case 11: BM = 64; BN = 64; break;
-        case 12: BM = 32; BN = 64; break;
-        default: BM = 64; BN = 16; break;
-    }
-}
-
-// a * b * c * e < 2^31 - 1 for positive factors, without overflowing on the way
-inline bool bytes_fit_31(long a, long b, long c, long e) {
-    const long lim = 0x7fffffffL;
-    if (a <= 0 || b <= 0 || c <= 0 || e <= 0) return false;
-    if (a >= lim / b) return false;
-    a *= b;
-    if (a >= lim / c) return false;
-    a *= c;
-    return a < lim / e;
-}
-
-bool fill_params(const mcav_igemm_desc* d, IgemmParams& p, int& tile) {
-    if (!d || !d->x1 || !d->w || !d->y) return false;
-    if (d->B <= 0 || d->Hs <= 0 || d->Ws <= 0 || d->Hd <= 0 || d->Wd <= 0 || d->C1 <= 0 || d->C2 < 0) return false;
-    if (d->C2 > 0 && !d->x2) return false;
-    if (d->kh <= 0 || d->kw <= 0 || d->Np <= 0 || d->Kp <= 0 || d->kh * d->kw > 64) return false;
-    if (d->n_begin < 0 || d->n_count <= 0 || d->n_begin + d->n_count > d->Np) return false;
-    // the destination: channels [y_choff, y_choff + n_count) of a pixel of Cd floats (a launch that ran past Cd would spill into the next pixel)
-    if (d->Cd <= 0 || d->y_choff < 0 || d->y_choff > d->Cd - d->n_count) return false;
-    if (d->mode == MCAV_G_SMALLC) { if (d->Kp != 4 || d->C1 != 4 || d->C2 != 0) return false; }
-    else if (d->Kp % CK != 0 || d->Kp < d->C1 + d->C2) return false;
-    if (d->C2 > 0 && (d->C1 % 4 != 0)) return false;
-    if (d->mode == MCAV_G_ADJ_REFLECT && (d->kh != 3 || d->kw != 3 || d->Hs != d->Hd || d->Ws != d->Wd || d->Hs < 2 || d->Ws < 2)) return false;
-    if (d->pad_mode == MCAV_PAD_REFLECT && (d->Hs < 2 || d->Ws < 2)) return false;
-    if (d->up1 && ((d->Hs & 1) || (d->Ws & 1))) return false;
-    if (d->pool && ((d->Hd & 1) || (d->Wd & 1) || d->mode == MCAV_G_ADJ_STRIDE2)) return false;
-    if (d->pool && d->stats) return false;
-    p.g.x1 = d->x1; p.g.x2 = d->x2; p.g.B = d->B; p.g.Hs = d->Hs; p.g.Ws = d->Ws; p.g.C1 = d->C1; p.g.C2 = d->C2; p.g.up1 = d->up1;
-    p.g.mode = d->mode; p.g.stride = d->stride; p.g.sign = d->sign; p.g.offset = d->offset; p.g.pad_mode = d->pad_mode;
-    p.w = d->w; p.kh = d->kh; p.kw = d->kw; p.Kp = d->Kp; p.taps = d->kh * d->kw; p.Kstride = kstride_of(p.taps, d->Kp);
-    p.y = d->y; p.Hd = d->Hd; p.Wd = d->Wd; p.Cd = d->Cd; p.n_begin = d->n_begin; p.n_count = d->n_count; p.y_choff = d->y_choff;
-    p.bias = d->bias; p.act = d->act; p.dact_aux = d->dact_aux; p.dact = d->dact; p.addend = d->addend; p.pool = d->pool; p.stats = d->stats;
-    if (d->stats_x && (!d->stats || !d->stats_mean || !d->stats_invstd || d->pool || d->y_choff != 0 || d->n_begin != 0 || d->n_count != d->Cd)) return false;
-    p.stats_x = d->stats ? d->stats_x : nullptr; p.stats_mean = d->stats_mean; p.stats_invstd = d->stats_invstd;
-    const long Mlin = (long)d->B * d->Hd * d->Wd;
-    if ((long)d->B * d->Hs * d->Ws * (d->C1 > d->C2 ? d->C1 : d->C2) * 4 >= 0x7fffffffL) return false;   // 32-bit byte offsets
-    if ((long)d->Np * kstride_of(d->kh * d->kw, d->Kp) * 4 >= 0x7fffffffL) return false;
-    // ... and so has the destination (the pooled one where pool is set): the lean epilogue, the halo and the stem kernels address y -- and
-    // dact_aux, addend, stats_x, which share its layout -- through 32-bit byte offsets
-    if (!bytes_fit_31((long)d->B, d->pool ? d->Hd >> 1 : d->Hd, d->pool ? d->Wd >> 1 : d->Wd, (long)d->Cd * 4)) return false;
-    p.no_tab = (d->tile >> 8) & 1;
-    p.ksplit = 1; p.kslab = nullptr;
-    p.wm = d->w_upmerge; p.Np_all = d->Np; p.upm = 0;
-    tile = pick_tile(d, Mlin) & 0xff;
-    if (tile == 0) { mcav_igemm_desc dd = *d; dd.tile = 0; tile = pick_tile(&dd, Mlin); }
-    if (((tile >= 8 && tile <= 10) || tile == 12) && (d->mode == MCAV_G_SMALLC || d->Kp % 32 != 0)) return false;      // 32-deep K-tiles need Kp % 32 == 0
-    if (tile == 11 && (d->mode == MCAV_G_SMALLC || d->Kp % 64 != 0)) return false;
-    int BM, BN;
-    tile_dims(tile, BM, BN);
-    p.groups = d->groups > 1 ? d->groups : 1;
-    if (p.groups > 1) {
-        if ((d->mode != MCAV_G_DIRECT && d->mode != MCAV_G_SMALLC) || d->pool || d->B % p.groups != 0) return false;
-        p.Mc = (int)(Mlin / p.groups);
-        p.McP = round_up(p.Mc, BM);
-        p.M = p.groups * p.McP;
-    } else if (d->mode == MCAV_G_ADJ_STRIDE2) {
-        p.Mc = d->B * ((d->Hd + 1) / 2) * ((d->Wd + 1) / 2);
-        p.McP = round_up(p.Mc, BM);
-        p.M = 4 * p.McP;
-    } else {
-        p.Mc = 0; p.McP = 1;
-        if (Mlin > 0x7fffffffL) return false;
-        p.M = (int)Mlin;
-        // merged-tap upsample (see mcav_igemm_desc.w_upmerge): everything the table-driven UPM kernel needs must hold, else the plain path
-        const int ck = (tile >= 8 && tile <= 10) || tile == 12 ? 32 : (tile == 11 ? 64 : 16);
-        if (d->w_upmerge && d->mode == MCAV_G_DIRECT && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->sign == 1 && d->offset == -1 &&
-            d->pad_mode == MCAV_PAD_REFLECT && d->up1 == 1 && d->C2 > 0 && !(d->Hd & 1) && !(d->Wd & 1) && d->Hd == d->Hs && d->Wd == d->Ws &&
-            !d->pool && !d->stats && d->C1 % ck == 0 && d->C2 % ck == 0 && d->C1 + d->C2 == d->Kp && (d->C1 & 3) == 0 && !p.no_tab &&
-            (long)4 * d->Np * 4 * d->C1 * 4 < 0x7fffffffL) {
-            p.upm = 1;
-            p.bm = BM;
-            p.Mc = d->B * (d->Hd / 2) * (d->Wd / 2);
-            p.McP = round_up(p.Mc, BM);
-            p.M = 4 * p.McP;
-        }
-    }
-    p.mtiles = (p.M + BM - 1) / BM;
-    p.ntiles = (d->n_count + BN - 1) / BN;
-    return true;
-}
-
 // y = epilogue(sum of the K-split partials): one element per thread and pass, fixed summation order
 __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restrict__ slab, int splits, size_t n, int Cd, float* __restrict__ y,
                                                             const float* __restrict__ bias, int n_begin, int act, const float* __restrict__ dact_aux,
@@ -1929,43 +1803,26 @@ inline float* ksplit_slab(hipStream_t s, size_t bytes) {
     return reinterpret_cast<float*>(e.first);
 }
 
-template <class T>
-inline void launch_igemm(const IgemmParams& p_in, hipStream_t s) {
-    IgemmParams p = p_in;
-    p.ksplit = 1; p.kslab = nullptr;
-    const bool c4ok = (p.g.C1 & 3) == 0 && (p.g.C2 & 3) == 0 && (p.g.C2 == 0 || (p.g.C1 & 15) == 0);
-    const bool fast_mode = p.g.mode == MCAV_G_DIRECT || (p.g.mode == MCAV_G_ADJ_STRIDE2 && p.g.C2 == 0) || p.g.mode == MCAV_G_SMALLC;
-    const bool tab = (p.g.mode == MCAV_G_DIRECT || (p.g.mode == MCAV_G_ADJ_STRIDE2 && p.g.C2 == 0)) && c4ok && p.taps <= TAB_TAPS &&
-                     p.g.C1 + p.g.C2 == p.Kp && p.Kp % T::KD == 0 && (p.g.C2 == 0 || p.g.C1 % T::KD == 0) && !p.no_tab;
-    // (tall tiles put rows of many image lines into one wavefront: most wavefronts would take the border path, so they keep the general kernel)
-    const bool tab_refl = p.g.mode == MCAV_G_ADJ_REFLECT && c4ok && p.g.C2 == 0 && p.g.C1 == p.Kp && p.Kp % T::KD == 0 && !p.no_tab && T::AROWS <= 2;
-    if (tab && !p.upm) {
-        // A handful of tiles with a long K loop (PoseNet conv5-7 and their data gradients: 2 .. 90 tiles of 36 .. 72 K-tiles, one workgroup
-        // per CU working through them alone): K is cut over up to 8 workgroups per tile, splitk_finish_kernel sums the partials (fixed order)
-        // and applies the epilogue.
-        const bool plain = !p.pool && !p.stats && p.groups <= 1 && p.y_choff == 0 && p.n_count == p.Cd && p.n_begin == 0;
-        const int tiles = p.mtiles * p.ntiles, ktiles = p.Kp / T::KD * p.taps;
-        static const int enabled = MCAV_KNOB_INT("MCAV_KSPLIT", 1);
-        static const int max_tiles = MCAV_KNOB_INT("MCAV_KSPLIT_TILES", 256);
-        if (enabled && plain && tiles <= max_tiles && ktiles >= 32) {
-            int ksp = 1024 / tiles;
-            if (ksp > 8) ksp = 8;
-            if (ksp > ktiles / 4) ksp = ktiles / 4;
-            if (ksp >= 2) {
-                float* slab = ksplit_slab(s, (size_t)p.g.B * p.Hd * p.Wd * p.Cd * 4 * ksp);
-                if (slab) { p.ksplit = ksp; p.kslab = slab; }
-            }
-        }
+// the fp32 family: the kernel plan_fp32 chose, on tile config ID; the K-split it planned runs where its slab exists
+template <class T, int ID>
+inline void launch_igemm(const IgemmRoute& r, hipStream_t s) {
+    static_assert(T::BM == tile_bm(ID) && T::BN == tile_bn(ID) && T::KD == tile_kd(ID) && T::AROWS == tile_arows(ID), "conv_plan.h's tile table");
+    IgemmParams p = r.p;
+    if (r.ksplit > 1) {
+        float* slab = ksplit_slab(s, (size_t)p.g.B * p.Hd * p.Wd * p.Cd * 4 * r.ksplit);
+        if (slab) { p.ksplit = r.ksplit; p.kslab = slab; }
     }
     const int grid = p.mtiles * p.ntiles * p.ksplit;
     const size_t tab_bytes = sizeof(unsigned) * (size_t)p.taps * T::BM * (p.g.C2 > 0 ? 2 : 1);
     const size_t refl_bytes = sizeof(unsigned) * (size_t)p.taps * T::BM * 4;      // + the three tables of reflected sources
-    if (p.upm) timed_launch(igemm_tab_kernel<T, 2>, grid, dim3(256), sizeof(unsigned) * 13 * T::BM, s, p);
-    else if (tab) timed_launch(igemm_tab_kernel<T, 0>, grid, dim3(256), tab_bytes, s, p);
-    else if (tab_refl) timed_launch(igemm_tab_kernel<T, 1>, grid, dim3(256), refl_bytes, s, p);
-    else if (fast_mode && c4ok) timed_launch(igemm_kernel<T, K_FAST>, grid, dim3(256), 0, s, p);
-    else if (p.g.mode == MCAV_G_ADJ_REFLECT && c4ok && p.g.C2 == 0) timed_launch(igemm_kernel<T, K_REFLADJ>, grid, dim3(256), 0, s, p);
-    else timed_launch(igemm_kernel<T, K_GENERIC>, grid, dim3(256), 0, s, p);
+    switch (r.variant) {
+        case MCAV_RV_TABLE | MCAV_RV_UPM: timed_launch(igemm_tab_kernel<T, 2>, grid, dim3(256), sizeof(unsigned) * 13 * T::BM, s, p); break;
+        case MCAV_RV_TABLE: timed_launch(igemm_tab_kernel<T, 0>, grid, dim3(256), tab_bytes, s, p); break;
+        case MCAV_RV_TABLE | MCAV_RV_REFLECT | MCAV_RV_ADJ: timed_launch(igemm_tab_kernel<T, 1>, grid, dim3(256), refl_bytes, s, p); break;
+        case MCAV_RV_FAST: timed_launch(igemm_kernel<T, K_FAST>, grid, dim3(256), 0, s, p); break;
+        case MCAV_RV_REFLECT | MCAV_RV_ADJ: timed_launch(igemm_kernel<T, K_REFLADJ>, grid, dim3(256), 0, s, p); break;
+        default: timed_launch(igemm_kernel<T, K_GENERIC>, grid, dim3(256), 0, s, p); break;
+    }
     if (p.ksplit > 1) {
         const size_t n = (size_t)p.g.B * p.Hd * p.Wd * p.Cd;
         const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
@@ -1974,267 +1831,134 @@ inline void launch_igemm(const IgemmParams& p_in, hipStream_t s) {
     }
 }
 
+// the fp32 slab GEMM of the weight gradient on tile config ID
+template <class T, int ID>
+inline void launch_wgrad(const WgradRoute& r, hipStream_t s) {
+    static_assert(T::BM == tile_bm(ID) && T::BN == tile_bn(ID), "conv_plan.h's tile table");
+    const WgradParams& p = r.pl.p;
+    const int grid = p.splits * p.mtiles * p.ntiles;
+    if (r.variant & MCAV_RV_TABLE) {
+        if (p.upm) timed_launch(wgrad_tab_kernel<T, true>, grid, dim3(256), 0, s, p);
+        else timed_launch(wgrad_tab_kernel<T, false>, grid, dim3(256), 0, s, p);
+    } else if (r.variant & MCAV_RV_FAST) {
+        timed_launch(wgrad_kernel<T, K_FAST>, grid, dim3(256), 0, s, p);
+    } else {
+        timed_launch(wgrad_kernel<T, K_GENERIC>, grid, dim3(256), 0, s, p);
+    }
+}
+
 }  // namespace mcav
 
 using namespace mcav;
 
-int mcav_bf16_igemm_mtiles(const mcav_igemm_desc* d);             // conv_bf16.hip: 0 = the launch does not run there
-int mcav_patch_f32_mtiles(const mcav_igemm_desc* d);              // conv_bf16.hip: blocks of the fp32 patch-in-LDS kernel, 0 = not one of its launches
-bool mcav_try_patch_f32(const mcav_igemm_desc* d, hipStream_t s);
-int mcav_stem_mtiles(const mcav_igemm_desc* d);                   // conv_stem.hip: 0 = not the image stem
+// the other families' launches: each takes the route as planned and decides nothing
+void mcav_halo_launch(const IgemmRoute& r, hipStream_t s);            // conv_halo.hip
+void mcav_stem_launch(const IgemmRoute& r, hipStream_t s);            // conv_stem.hip
+int mcav_patch_bf16_launch(const IgemmRoute& r, hipStream_t s);       // conv_bf16.hip: the fp32 patch kernel and the four bf16 families
+void mcav_halo_wgrad_launch(const WgradRoute& r, hipStream_t s);
+void mcav_stem_wgrad_launch(const WgradRoute& r, hipStream_t s);
+void mcav_bf16_wgrad_launch(const WgradParams& p, hipStream_t s);
 
-int mcav_stem_planar_igemm(const mcav_igemm_desc* d);      // conv_stem.hip
-
-MCAV_EXPORT int mcav_igemm_mtiles(const mcav_igemm_desc* d) {
-    IgemmParams p;
-    int tile;
-    const int planar = mcav_stem_planar_igemm(d);
-    if (planar < 0) return MCAV_E_INVALID;
-    mcav_igemm_desc dp;
-    if (planar) { dp = *d; if (!dp.x1) dp.x1 = d->x_planar[0]; d = &dp; }
-    if (!fill_params(d, p, tile)) return MCAV_E_INVALID;
-    if (const int st = mcav_stem_mtiles(d)) return st;             // the stem kernel's 8 x 32 output tiles
-    if (const int pt = mcav_patch_f32_mtiles(d)) return pt;         // the fp32 patch-in-LDS kernel's blocks (conv_bf16.hip)
-    if (d->mma != 0) {                              // the bf16 kernels choose their own tile shape
-        const int mt = mcav_bf16_igemm_mtiles(d);
-        if (mt > 0) return mt;
-    }
-    return p.mtiles;
+// what the planner takes from the machine, asked once (no device: the MI355X's count)
+static const PlanEnv& plan_env() {
+    static const PlanEnv env = [] {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        const int n = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+        (void)hipGetLastError();
+        return PlanEnv{n};
+    }();
+    return env;
 }
 
-bool mcav_try_halo(const mcav_igemm_desc* d, hipStream_t s);      // conv_halo.hip: narrow high-resolution 3x3 layers (forward and reflect-adjoint)
-int mcav_bf16_igemm(const mcav_igemm_desc* d, hipStream_t s);      // conv_bf16.hip: 1 = not eligible
-bool mcav_try_stem(const mcav_igemm_desc* d, const mcav::IgemmParams& p, hipStream_t s);      // conv_stem.hip: the 7x7 stride-2 image stem
-int mcav_stem_mtiles(const mcav_igemm_desc* d);
-int mcav_stem_planar_igemm(const mcav_igemm_desc* d);      // the x_planar fields: 0 = not set, 1 = a stem kernel reads them, -1 = refused
-bool mcav_bf16_wgrad_plan(const mcav_wgrad_desc* d, mcav::WgradPlan& pl);
-void mcav_bf16_wgrad_launch(const mcav::WgradParams& p, hipStream_t s);
+MCAV_EXPORT int mcav_igemm_route(const mcav_igemm_desc* d, mcav_conv_route* out) {
+    if (!out) return MCAV_E_INVALID;
+    *out = mcav_conv_route{};
+    IgemmRoute r;
+    const int rc = plan_igemm(d, plan_env(), r);
+    if (rc == MCAV_OK) *out = mcav_conv_route{r.family, r.variant, r.tile, r.mtiles, r.ntiles, r.workgroups, r.ksplit > 1 ? r.ksplit : 1, 0};
+    return rc;
+}
+
+MCAV_EXPORT int mcav_igemm_mtiles(const mcav_igemm_desc* d) {
+    IgemmRoute r;
+    const int rc = plan_igemm(d, plan_env(), r);
+    return rc == MCAV_OK ? r.mtiles : rc;
+}
+
+MCAV_EXPORT int mcav_igemm_uses_bf16(const mcav_igemm_desc* d) { return igemm_uses_bf16(d); }
 
 MCAV_EXPORT int mcav_igemm(const mcav_igemm_desc* d, void* stream) {
-    IgemmParams p;
-    int tile;
-    const int planar = mcav_stem_planar_igemm(d);      // NCHW image sources: only the two stem kernels read them (x1 may then be NULL)
-    if (planar < 0) return MCAV_E_INVALID;
-    mcav_igemm_desc dp;
-    if (planar) { dp = *d; if (!dp.x1) dp.x1 = d->x_planar[0]; d = &dp; }      // (a non-null stand-in for the checks below; never read)
-    if (!fill_params(d, p, tile)) return MCAV_E_INVALID;
+    IgemmRoute r;
+    const int rc = plan_igemm(d, plan_env(), r);
+    if (rc != MCAV_OK) return rc;
     hipStream_t s = as_stream(stream);
-    if (planar) return mcav_try_stem(d, p, s) ? launch_status() : MCAV_E_INVALID;
-    if (mcav_try_halo(d, s)) return launch_status();
-    if (mcav_try_stem(d, p, s)) return launch_status();
-    if (mcav_try_patch_f32(d, s)) return launch_status();
-    if (d->mma != 0) {                    // bf16 MFMA tiles (conv_bf16.hip) where the launch qualifies, else the fp32 kernels below
-        const int rc = mcav_bf16_igemm(d, s);
-        if (rc != 1) return rc;
-    }
-    switch (tile) {
-        case 1: launch_igemm<Tile128x64>(p, s); break;
-        case 2: launch_igemm<Tile64x64>(p, s); break;
-        case 3: launch_igemm<Tile256x32>(p, s); break;
-        case 4: launch_igemm<Tile256x16>(p, s); break;
-        case 5: launch_igemm<Tile128x128>(p, s); break;
-        case 6: launch_igemm<Tile64x16>(p, s); break;
-        case 7: launch_igemm<Tile128x32>(p, s); break;
-        case 8: launch_igemm<Tile128x64k32>(p, s); break;
-        case 9: launch_igemm<Tile128x128k32>(p, s); break;
-        case 10: launch_igemm<Tile64x64k32>(p, s); break;
-        case 11: launch_igemm<Tile64x64k64>(p, s); break;
-        case 12: launch_igemm<Tile32x64k32>(p, s); break;
-        default: return MCAV_E_INVALID;
+    switch (r.family) {
+        case MCAV_IGEMM_HALO: mcav_halo_launch(r, s); break;
+        case MCAV_IGEMM_STEM: mcav_stem_launch(r, s); break;
+        case MCAV_IGEMM_FP32:
+            switch (r.tile) {
+                case 1: launch_igemm<Tile128x64, 1>(r, s); break;
+                case 2: launch_igemm<Tile64x64, 2>(r, s); break;
+                case 3: launch_igemm<Tile256x32, 3>(r, s); break;
+                case 4: launch_igemm<Tile256x16, 4>(r, s); break;
+                case 5: launch_igemm<Tile128x128, 5>(r, s); break;
+                case 6: launch_igemm<Tile64x16, 6>(r, s); break;
+                case 7: launch_igemm<Tile128x32, 7>(r, s); break;
+                case 8: launch_igemm<Tile128x64k32, 8>(r, s); break;
+                case 9: launch_igemm<Tile128x128k32, 9>(r, s); break;
+                case 10: launch_igemm<Tile64x64k32, 10>(r, s); break;
+                case 11: launch_igemm<Tile64x64k64, 11>(r, s); break;
+                case 12: launch_igemm<Tile32x64k32, 12>(r, s); break;
+                default: return MCAV_E_INVALID;
+            }
+            break;
+        default: return mcav_patch_bf16_launch(r, s);
     }
     return launch_status();
 }
 
-namespace mcav {
-
-}  // namespace mcav
-int mcav_stem_wgrad_splits(const mcav_wgrad_desc* d);
-int mcav_stem_planar_wgrad(const mcav_wgrad_desc* d);      // the x_planar fields: 0 = not set, 1 = a stem kernel reads them, -1 = refused
-int mcav_stem_wgrad_bn(const mcav_wgrad_desc* d);      // the dy_bn_* fields: 0 = not set, 1 = the depth stem kernel applies them, -1 = refused
-void mcav_stem_wgrad_launch(const mcav_wgrad_desc* d, float* slab, int Ktot, int slabN, int splits, hipStream_t s);
-int mcav_halo_wgrad_splits(const mcav_wgrad_desc* d);
-void mcav_halo_wgrad_launch(const mcav_wgrad_desc* d, float* slab, int slabN, int splits, hipStream_t s);
-namespace mcav {
-
-bool plan_wgrad(const mcav_wgrad_desc* d, WgradPlan& pl) {
-    if (!d || !d->x1 || !d->dy || !d->dw_oihw) return false;
-    if (d->B <= 0 || d->Hs <= 0 || d->Ws <= 0 || d->Hd <= 0 || d->Wd <= 0 || d->C1 <= 0 || d->C2 < 0 || d->Cout <= 0 || d->Cin <= 0) return false;
-    if (d->C2 > 0 && (!d->x2 || d->C1 % 4 != 0)) return false;
-    if (d->mode != MCAV_G_DIRECT && d->mode != MCAV_G_SMALLC) return false;
-    if (d->mode == MCAV_G_SMALLC && (d->Kp != 4 || d->C1 != 4 || d->C2 != 0)) return false;
-    if (d->mode == MCAV_G_DIRECT && (d->Kp % CK != 0 || d->Kp < d->C1 + d->C2)) return false;
-    if (d->Cin > d->Kp) return false;
-    if (d->kh <= 0 || d->kw <= 0) return false;
-    if (d->Cdy <= 0 || d->dy_choff < 0 || d->dy_choff > d->Cdy - d->Cout) return false;      // channels [dy_choff, dy_choff + Cout) of dy exist
-    if (d->ci_offset < 0 || d->ci_offset > (d->Cin_total > 0 ? d->Cin_total : d->Cin) - d->Cin) return false;      // the launch's input-channel window lies inside the OIHW gradient
-    WgradParams& p = pl.p;
-    p.g.x1 = d->x1; p.g.x2 = d->x2; p.g.B = d->B; p.g.Hs = d->Hs; p.g.Ws = d->Ws; p.g.C1 = d->C1; p.g.C2 = d->C2; p.g.up1 = d->up1;
-    p.g.mode = d->mode; p.g.stride = d->stride; p.g.sign = d->sign; p.g.offset = d->offset; p.g.pad_mode = d->pad_mode;
-    p.kh = d->kh; p.kw = d->kw; p.Kp = d->Kp; p.taps = d->kh * d->kw; p.Ktot = p.taps * d->Kp;
-    p.dy = d->dy; p.Hd = d->Hd; p.Wd = d->Wd; p.Cdy = d->Cdy; p.dy_choff = d->dy_choff; p.Cout = d->Cout;
-    p.CoutLoad = round_up(d->Cout, 4) <= d->Cdy - d->dy_choff ? round_up(d->Cout, 4) : d->Cout;
-    const long M = (long)d->B * d->Hd * d->Wd;
-    if (M > 0x7fffffffL) return false;
-    if ((long)d->B * d->Hs * d->Ws * (d->C1 > d->C2 ? d->C1 : d->C2) * 4 >= 0x7fffffffL || M * d->Cdy * 4 >= 0x7fffffffL) return false;
-    p.Mpix = (int)M;
-    p.slabN = round_up(d->Cout, 16);
-    p.upm = 0; p.Hf = d->Hd; p.Wf = d->Wd; p.patch = 0; p.split_planes = 0;
-    if (d->upm) {      // merged-tap upsample half: 16 (class, merged tap) x Kp rows, reduction over the low-resolution pixels
-        if (d->mode != MCAV_G_DIRECT || d->kh != 3 || d->kw != 3 || d->stride != 1 || d->sign != 1 || d->offset != -1 || d->pad_mode != MCAV_PAD_REFLECT ||
-            !d->up1 || d->C2 != 0 || d->Hd != d->Hs || d->Wd != d->Ws || (d->Hd & 1) || (d->Wd & 1) || d->dbias || d->Kp != d->C1 || (d->C1 & 15) ||
-            (d->Cdy & 3) || (d->dy_choff & 3) || (p.CoutLoad & 3))
-            return false;
-        p.upm = 1;
-        p.taps = 16; p.Ktot = 16 * d->Kp;
-        p.Hd = d->Hd / 2; p.Wd = d->Wd / 2;
-        p.Mpix = d->B * p.Hd * p.Wd;
-    }
-    int tile = d->tile & 0xff;
-    if (!tile) {
-        if (d->Cout <= 16) tile = round_up(p.Ktot, 64) < round_up(p.Ktot, 256) ? 6 : 4;
-        else if (d->Cout <= 32) tile = 7;      // 128x32 (48 KB of LDS, three workgroups per CU; 256x32 needs 80 KB): 16x25 -> 32 0.052 -> 0.044 ms
-        else tile = 2;            // 64x64 beats 128x64 on every layer shape of the step (tools/conv_bench.py wgrad)
-    }
-    if (p.upm) tile = d->Cout <= 16 ? 6 : 2;                     // 64-row tiles: a row tile never straddles a parity class (4 Kp rows each)
-    if (tile != 1 && tile != 2 && tile != 3 && tile != 4 && tile != 6 && tile != 7) return false;
-    pl.tile = tile;
-    int BM, BN;
-    tile_dims(tile, BM, BN);
-    p.mtiles = (p.Ktot + BM - 1) / BM;
-    p.ntiles = (d->Cout + BN - 1) / BN;
-    const int out_tiles = p.mtiles * p.ntiles;
-    static const int target_wgs = MCAV_KNOB_INT("MCAV_WGRAD_TARGET_WGS", 0);
-    int max_splits = (p.Mpix + 8 * KP - 1) / (8 * KP);           // at least 8 K-tiles each
-    if (max_splits > 512) max_splits = 512;
-    if (max_splits < 1) max_splits = 1;
-    int splits;
-    if (target_wgs > 0) {                                        // tuning knob: aim at that many workgroups
-        splits = (target_wgs + out_tiles - 1) / out_tiles;
-    } else {
-        // Whole generations of resident workgroups: 1044 workgroups on 1024 slots (128->128 at 24x80 with "about 1024") run a second
-        // generation for 2 % of the work (0.142 ms; 0.124 at twice the splits).  Take the fewest splits, from one generation's worth up to
-        // three, whose workgroup count fills its last generation to 95 % (else the best fill).
-        const int occ = tile == 2 ? 4 : (tile == 7 ? 3 : (tile == 6 ? 4 : 2)), slots = 256 * occ;
-        auto wgs_of = [&](int sp) {
-            const int pps = round_up((p.Mpix + sp - 1) / sp, KP);
-            return out_tiles * ((p.Mpix + pps - 1) / pps);
-        };
-        int lo = slots / out_tiles, hi = 3 * slots / out_tiles + 1;
-        if (lo < 1) lo = 1;
-        if (lo > max_splits) lo = max_splits;
-        if (hi > max_splits) hi = max_splits;
-        splits = lo;
-        double best = -1.0;
-        for (int sp = lo; sp <= hi; ++sp) {
-            const int w = wgs_of(sp), gens = (w + slots - 1) / slots;
-            const double fill = (double)w / ((double)gens * slots);
-            if (fill > best + 1e-9) { best = fill; splits = sp; }
-            if (fill >= 0.95) { splits = sp; break; }
-        }
-    }
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    p.pix_per_split = round_up((p.Mpix + splits - 1) / splits, KP);
-    // table-driven kernel: the per-workgroup offset table (pixels of a split x taps touched by a row tile x sources) must fit
-    pl.use_tab = false;
-    const int wave_ch = BM / 4;
-    const bool fast = d->mode == MCAV_G_DIRECT && (d->C1 & 3) == 0 && (d->C2 & 3) == 0 && (d->C2 == 0 || d->C1 % wave_ch == 0) &&
-                      (p.CoutLoad & 3) == 0 && (d->Cdy & 3) == 0 && (d->dy_choff & 3) == 0 && !((d->tile >> 8) & 1);
-    p.tab_cht_log2 = 20;
-    if (fast) {
-        int ntmax = 1;
-        for (int mt = 0; mt < p.mtiles; ++mt) {
-            const int lo = mt * BM / d->Kp, hi = (mt * BM + BM - 1) / d->Kp < p.taps - 1 ? (mt * BM + BM - 1) / d->Kp : p.taps - 1;
-            if (hi - lo + 1 > ntmax) ntmax = hi - lo + 1;
-        }
-        const int epp = p.upm ? ntmax + 1 : ntmax * (d->C2 > 0 ? 2 : 1);  // table entries per pixel (upm: + the dy offset)
-        if ((long)p.pix_per_split * epp <= WG_TABCAP) {
-            pl.use_tab = true;                                            // one chunk
-        } else if (epp <= 16) {
-            int lg = 2;                                                   // two half-buffers of 2^lg tiles: 2^lg * KP * epp <= WG_TABCAP / 2
-            while ((2 << lg) * KP * epp <= WG_TABCAP / 2) ++lg;
-            p.tab_cht_log2 = lg;
-            pl.use_tab = true;
-        }
-    }
-    p.splits = (p.Mpix + p.pix_per_split - 1) / p.pix_per_split;
-    if (p.upm && !pl.use_tab) return false;                      // the merged form exists in the table-driven kernel only
-    const int halo_splits = p.upm ? 0 : mcav_halo_wgrad_splits(d);      // narrow high-resolution layers: conv_halo.hip writes the slab partials
-    pl.use_halo = halo_splits > 0;
-    if (pl.use_halo) { p.splits = halo_splits; pl.use_tab = false; }
-    const int stem_splits = p.upm ? 0 : mcav_stem_wgrad_splits(d);      // the image stem: conv_stem.hip writes the slab partials
-    pl.use_stem = stem_splits > 0;
-    if (pl.use_stem) { p.splits = stem_splits; pl.use_tab = false; }
-    p.want_bias = d->dbias != nullptr;
-    pl.slab_bytes = align_up(sizeof(float) * (size_t)p.splits * (p.Ktot + 1) * p.slabN, 256);
-    pl.groups = p.splits > 8 ? 8 : 0;                            // two-level reduction above 8 splits
-    pl.per_group = pl.groups ? (p.splits + pl.groups - 1) / pl.groups : 0;
-    if (pl.groups) pl.groups = (p.splits + pl.per_group - 1) / pl.per_group;
-    pl.pre_bytes = align_up(sizeof(float) * (size_t)pl.groups * (p.Ktot + 1) * p.slabN, 256);
-    const int out_taps = p.upm ? 9 : p.taps;                     // filter taps written to OIHW
-    int ci_t = 32;                                               // 32 x (CI_T * taps + 1) floats of LDS <= 64 KB ...
-    while (ci_t > 1 && ci_t * out_taps > 480) ci_t >>= 1;
-    if (ci_t * out_taps > 480) return false;
-    const int co_tiles = (d->Cout + 31) / 32;                    // ... and enough blocks to fill the chip
-    while (ci_t > 1 && co_tiles * ((d->Cin + ci_t - 1) / ci_t) < 256) ci_t >>= 1;
-    pl.ci_t = ci_t;
-    return true;
+MCAV_EXPORT int mcav_wgrad_route(const mcav_wgrad_desc* d, mcav_conv_route* out) {
+    if (!out) return MCAV_E_INVALID;
+    *out = mcav_conv_route{};
+    WgradRoute r;
+    const int rc = plan_wgrad_route(d, plan_env(), r);
+    const WgradParams& p = r.pl.p;
+    if (rc == MCAV_OK)
+        *out = mcav_conv_route{r.family, r.variant, r.pl.tile, p.mtiles, p.ntiles, r.workgroups, p.splits, r.workspace_bytes()};
+    return rc;
 }
-
-template <class T>
-inline void launch_wgrad(const WgradParams& p, bool use_tab, hipStream_t s) {
-    const int grid = p.splits * p.mtiles * p.ntiles;
-    if (use_tab && p.upm) { timed_launch(wgrad_tab_kernel<T, true>, grid, dim3(256), 0, s, p); return; }
-    if (use_tab) { timed_launch(wgrad_tab_kernel<T, false>, grid, dim3(256), 0, s, p); return; }
-    const int wave_ch = T::BM / 4;          // channels one wavefront's A columns span
-    const bool fast = (p.g.mode == MCAV_G_DIRECT || p.g.mode == MCAV_G_SMALLC) && (p.g.C1 & 3) == 0 && (p.g.C2 & 3) == 0 && (p.g.C2 == 0 || p.g.C1 % wave_ch == 0) &&
-                      (p.CoutLoad & 3) == 0 && (p.Cdy & 3) == 0 && (p.dy_choff & 3) == 0 && p.Wd >= 16;
-    if (fast) timed_launch(wgrad_kernel<T, K_FAST>, grid, dim3(256), 0, s, p);
-    else timed_launch(wgrad_kernel<T, K_GENERIC>, grid, dim3(256), 0, s, p);
-}
-
-}  // namespace mcav
 
 MCAV_EXPORT size_t mcav_wgrad_workspace_bytes(const mcav_wgrad_desc* d) {
-    WgradPlan pl;
-    const int planar = mcav_stem_planar_wgrad(d);
-    if (mcav_stem_wgrad_bn(d) < 0 || planar < 0) return 0;
-    mcav_wgrad_desc dp;
-    if (planar) { dp = *d; if (!dp.x1) dp.x1 = d->x_planar[0]; d = &dp; }      // (a non-null stand-in for the planner's checks; never read)
-    const bool special = mcav_stem_wgrad_bn(d) || planar;
-    if (!(d && d->mma != 0 && !special && mcav_bf16_wgrad_plan(d, pl)) && !plan_wgrad(d, pl)) return 0;
-    if (special && !pl.use_stem) return 0;
-    return pl.slab_bytes + pl.pre_bytes;
+    WgradRoute r;
+    return plan_wgrad_route(d, plan_env(), r) == MCAV_OK ? r.workspace_bytes() : 0;
 }
 
 MCAV_EXPORT int mcav_wgrad_uses_bf16(const mcav_wgrad_desc* d) {
-    WgradPlan pl;
-    return d && d->mma != 0 && !mcav_stem_wgrad_bn(d) && !mcav_stem_planar_wgrad(d) && mcav_bf16_wgrad_plan(d, pl);
+    WgradRoute r;
+    return plan_wgrad_route(d, plan_env(), r) == MCAV_OK && (r.family == MCAV_WGRAD_BF16_PATCH || r.family == MCAV_WGRAD_BF16_TILE);
 }
 
 // the GEMM part of a weight gradient: partial tiles into the slab at `workspace`
-static int wgrad_gemm(const mcav_wgrad_desc* d, void* workspace, size_t workspace_bytes, hipStream_t s, WgradPlan& pl) {
-    const int bn = mcav_stem_wgrad_bn(d);      // only the depth stem's kernel folds a BatchNorm backward into its dy tile: every other path refuses the fields
-    const int planar = mcav_stem_planar_wgrad(d);      // only the two stem kernels read NCHW image sources (x1 may then be NULL)
-    if (bn < 0 || planar < 0) return MCAV_E_INVALID;
-    mcav_wgrad_desc dp;
-    if (planar) { dp = *d; if (!dp.x1) dp.x1 = d->x_planar[0]; d = &dp; }      // (a non-null stand-in for the planner's checks; never read)
-    const bool bf16 = d && d->mma != 0 && !bn && !planar && mcav_bf16_wgrad_plan(d, pl);      // bf16 MFMA tiles where the launch qualifies (conv_bf16.hip)
-    if ((!bf16 && !plan_wgrad(d, pl)) || !workspace) return MCAV_E_INVALID;
-    if ((bn || planar) && !pl.use_stem) return MCAV_E_INVALID;
-    if (workspace_bytes < pl.slab_bytes + pl.pre_bytes) return MCAV_E_WORKSPACE;
-    pl.p.slab = reinterpret_cast<float*>(workspace);
-    if (bf16) mcav_bf16_wgrad_launch(pl.p, s);
-    else if (pl.use_stem) mcav_stem_wgrad_launch(d, pl.p.slab, pl.p.Ktot, pl.p.slabN, pl.p.splits, s);
-    else if (pl.use_halo) mcav_halo_wgrad_launch(d, pl.p.slab, pl.p.slabN, pl.p.splits, s);
-    else switch (pl.tile) {
-        case 1: launch_wgrad<Tile128x64>(pl.p, pl.use_tab, s); break;
-        case 2: launch_wgrad<Tile64x64>(pl.p, pl.use_tab, s); break;
-        case 3: launch_wgrad<Tile256x32>(pl.p, pl.use_tab, s); break;
-        case 4: launch_wgrad<Tile256x16>(pl.p, pl.use_tab, s); break;
-        case 6: launch_wgrad<Tile64x16>(pl.p, pl.use_tab, s); break;
-        case 7: launch_wgrad<Tile128x32>(pl.p, pl.use_tab, s); break;
-        default: return MCAV_E_INVALID;
+static int wgrad_gemm(const mcav_wgrad_desc* d, void* workspace, size_t workspace_bytes, hipStream_t s, WgradRoute& r) {
+    if (plan_wgrad_route(d, plan_env(), r) != MCAV_OK || !workspace) return MCAV_E_INVALID;
+    if (workspace_bytes < r.workspace_bytes()) return MCAV_E_WORKSPACE;
+    r.pl.p.slab = reinterpret_cast<float*>(workspace);
+    switch (r.family) {
+        case MCAV_WGRAD_BF16_PATCH:
+        case MCAV_WGRAD_BF16_TILE: mcav_bf16_wgrad_launch(r.pl.p, s); break;
+        case MCAV_WGRAD_STEM: mcav_stem_wgrad_launch(r, s); break;
+        case MCAV_WGRAD_HALO: mcav_halo_wgrad_launch(r, s); break;
+        default:
+            switch (r.pl.tile) {
+                case 1: launch_wgrad<Tile128x64, 1>(r, s); break;
+                case 2: launch_wgrad<Tile64x64, 2>(r, s); break;
+                case 3: launch_wgrad<Tile256x32, 3>(r, s); break;
+                case 4: launch_wgrad<Tile256x16, 4>(r, s); break;
+                case 6: launch_wgrad<Tile64x16, 6>(r, s); break;
+                case 7: launch_wgrad<Tile128x32, 7>(r, s); break;
+                default: return MCAV_E_INVALID;
+            }
     }
     return MCAV_OK;
 }
@@ -2259,12 +1983,12 @@ static void fill_reduce_item(const mcav_wgrad_desc* d, const WgradPlan& pl, void
 }
 
 MCAV_EXPORT int mcav_wgrad(const mcav_wgrad_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
-    WgradPlan pl;
+    WgradRoute r;
     hipStream_t s = as_stream(stream);
-    const int rc = wgrad_gemm(d, workspace, workspace_bytes, s, pl);
+    const int rc = wgrad_gemm(d, workspace, workspace_bytes, s, r);
     if (rc != MCAV_OK) return rc;
     mcav_wgrad_reduce_item it;
-    fill_reduce_item(d, pl, workspace, it);
+    fill_reduce_item(d, r.pl, workspace, it);
     const size_t lds_bytes = sizeof(float) * 32 * (size_t)(it.ci_t * it.taps + 1);
     const float* rsrc = it.slab;
     int rsplits = it.splits;
@@ -2282,10 +2006,10 @@ MCAV_EXPORT int mcav_wgrad(const mcav_wgrad_desc* d, void* workspace, size_t wor
 
 MCAV_EXPORT int mcav_wgrad_deferred(const mcav_wgrad_desc* d, void* workspace, size_t workspace_bytes, mcav_wgrad_reduce_item* item, void* stream) {
     if (!item) return MCAV_E_INVALID;
-    WgradPlan pl;
-    const int rc = wgrad_gemm(d, workspace, workspace_bytes, as_stream(stream), pl);
+    WgradRoute r;
+    const int rc = wgrad_gemm(d, workspace, workspace_bytes, as_stream(stream), r);
     if (rc != MCAV_OK) return rc;
-    fill_reduce_item(d, pl, workspace, *item);
+    fill_reduce_item(d, r.pl, workspace, *item);
     return launch_status();
 }
 

@@ -1,5 +1,5 @@
-// Pieces shared by the fp32 (conv_igemm.hip) and bf16 (conv_bf16.hip) implicit-GEMM kernels: tile shapes, the row decoder, the epilogue,
-// the weight-gradient parameter block and the host-side planners.
+// Pieces shared by the fp32 (conv_igemm.hip) and bf16 (conv_bf16.hip) implicit-GEMM kernels: tile shapes, the row decoder, the epilogue.
+// (The parameter blocks and the host-side planners: conv_plan.h.)
 #pragma once
 #include <stdlib.h>
 #include <type_traits>
@@ -327,47 +327,5 @@ __device__ __forceinline__ void igemm_epilogue_lean(const IgemmParams& p, typena
         }
     }
 }
-
-constexpr int TAB_TAPS = 32;     // 3x3 filters, the 4x4 stride-2 form of the pooled upsample adjoint, PoseNet's 5x5
-constexpr int WG_TABCAP = 2048;
-
-struct WgradParams {
-    GatherSrc g;
-    int kh, kw, Kp, taps, Ktot;   // Ktot = taps * Kp (GEMM rows)
-    const float* dy;
-    int Hd, Wd, Cdy, dy_choff, Cout;
-    int CoutLoad;                  // Cout rounded up to 4 when dy physically has those (zero) channels
-    int Mpix;                      // B * Hd * Wd
-    int splits, pix_per_split;     // pixel ranges per workgroup (multiple of KP)
-    int mtiles, ntiles;
-    float* slab;                   // [splits][Ktot + 1][slabN]; row Ktot holds the per-split column sums of dy (bias gradient)
-    int slabN;                     // row stride of the slab (Cout rounded up to 16)
-    int want_bias;
-    int tab_cht_log2;              // wgrad_tab_kernel: log2 of the tiles per table chunk (>= 20: the whole split is one chunk)
-    int upm;                       // merged-tap upsample (mcav_wgrad_desc.upm): rows = 16 (class, merged tap) x Kp, pixels = LOW-resolution ones
-    int Hf, Wf;                    // upm: full-resolution size of dy (Hd, Wd hold the low-resolution one)
-    int split_planes;              // conv_bf16.hip: 1 = the fp32 contraction on three bf16 planes per operand (mcav_wgrad_desc.mma = 2)
-    // conv_bf16.hip, wgrad3x3_patch_kernel (patch = 1): pixel blocks of TH x TW (<= 64 pixels) of one image, `bps` consecutive blocks per split,
-    // workgroup = (split, 64 input x 64 output channels)
-    int patch, pTH, pTW, ptiles_y, ptiles_x, prefl, pnblocks, pbps, pct_co, pnarrow;
-};
-
-constexpr int KP = 32;   // pixels per K-tile of the wgrad GEMM
-
-struct WgradPlan {
-    WgradParams p;
-    int tile;
-    bool use_tab;
-    bool use_halo;
-    bool use_stem;                 // conv_stem.hip: the 7x7 stride-2 image stem's own weight-gradient kernel
-    size_t slab_bytes, pre_bytes;
-    int ci_t, groups, per_group;
-};
-
-
-// host-side planners (conv_igemm.hip)
-bool fill_params(const mcav_igemm_desc* d, IgemmParams& p, int& tile);
-bool plan_wgrad(const mcav_wgrad_desc* d, WgradPlan& pl);
-void tile_dims(int id, int& BM, int& BN);
 
 }  // namespace mcav

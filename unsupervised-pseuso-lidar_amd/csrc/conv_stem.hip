@@ -16,7 +16,6 @@
 
 namespace mcav {
 
-constexpr int ST_TW = 32;                         // output tile width (one MFMA row block)
 constexpr int ST_PC = 36;                         // floats per parity plane row: indices px + kxp <= 31 + 3, padded
 
 // C real input channels stored in pixels of CP floats; N output channels (64: two 32-wide column tiles per wavefront; 16: one, the upper
@@ -33,6 +32,7 @@ struct StemCfg {
 };
 using StemDepth = StemCfg<3, 4, 64, 8>;           // torchvision conv1 on the NHWC4 image
 using StemPose = StemCfg<9, 16, 16, 4>;           // PoseNet conv1 on the 16-channel (9 real) input pack
+static_assert(StemDepth::TH == ST_TH_DEPTH && StemPose::TH == ST_TH_POSE, "conv_plan.h counts the stems' tiles");
 
 // mcav_igemm_desc / mcav_wgrad_desc .x_planar: the stem reads the NCHW images themselves -- up to three contiguous [Bp][3][Hs][Ws] tensors --
 // instead of an NHWC copy packed for it.  The patch is split into per-channel LDS planes anyway, so a channel plane of the image is the layout
@@ -465,7 +465,6 @@ __global__ void pack_stem_weights_kernel(const float* __restrict__ w, float* __r
 // lane-constant LDS offset (channel plane, source row ky, parity plane, column pair) -- 32 consecutive k land on 32 different banks -- and the
 // pixel adds an immediate, so the loop body is again ds_read_b32 + MFMA.  Each workgroup writes one slab partial in the layout the shared
 // reduction expects (row = tap * 4 + channel).
-constexpr int SW_TH = 4;                          // output rows per tile
 constexpr int SW_PR = 2 * SW_TH + 5;              // 13 source rows
 
 // C / CP / N as in the forward kernel; KP = the filter's K padding in the slab layout (row = tap * KP + channel).  The 2 KS k rows are
@@ -652,33 +651,6 @@ __global__ __launch_bounds__(256) void stem7x7s2_wgrad_kernel(const float* __res
     }
 }
 
-// which stem this forward launch is: 1 = the depth net's image stem (SMALLC, 3 -> 64), 2 = PoseNet conv1 (9 of 16 channels -> 16), 0 = neither
-static int stem_kind(const mcav_igemm_desc* d) {
-    if (!d || !d->w_stem || d->kh != 7 || d->kw != 7 || d->stride != 2 || d->sign != 1 || d->offset != -3 || d->C2 != 0 || d->n_begin != 0 ||
-        d->pool || d->dact_aux || d->addend || d->y_choff != 0 || ((d->tile >> 9) & 1) || d->pad_mode != MCAV_PAD_ZERO ||
-        d->Hd != (d->Hs - 1) / 2 + 1 || d->Wd != (d->Ws - 1) / 2 + 1)
-        return 0;
-    if (d->mode == MCAV_G_SMALLC && d->C1 == 4 && d->n_count == 64 && d->Np == 64) return 1;
-    if (d->mode == MCAV_G_DIRECT && d->C1 == 16 && d->Kp == 16 && d->n_count == 16 && d->Np == 16 && !d->stats && !d->up1) return 2;
-    return 0;
-}
-
-// the x_planar fields of either descriptor for a launch of stem kind `kind`: 0 = not set, 1 = set and launchable, -1 = refused
-template <class D>
-static int stem_planar_state(const D* d, int kind) {
-    if (!d->x_planar[0] && !d->x_planar[1] && !d->x_planar[2] && !d->planar_B && !d->planar_stack) return 0;
-    if (d->planar_B <= 0 || !d->x_planar[0]) return -1;
-    if (kind == 1) {                                      // batch-stacked RGB images
-        const int ns = d->B / d->planar_B;
-        if (d->planar_stack != 1 || d->B % d->planar_B || ns > 3) return -1;
-        for (int i = 0; i < ns; ++i)
-            if (!d->x_planar[i]) return -1;
-        return 1;
-    }
-    if (kind == 2) return d->planar_stack == 2 && d->planar_B == d->B && d->x_planar[1] && d->x_planar[2] ? 1 : -1;
-    return -1;
-}
-
 template <class D>
 static StemPlanar stem_planar_args(const D* d) {
     StemPlanar pl = {};
@@ -691,50 +663,32 @@ static StemPlanar stem_planar_args(const D* d) {
 
 using namespace mcav;
 
-int mcav_stem_planar_igemm(const mcav_igemm_desc* d) { return d ? stem_planar_state(d, stem_kind(d)) : 0; }
-
-int mcav_stem_mtiles(const mcav_igemm_desc* d) {      // 0 = not this kernel's launch
-    const int kind = stem_kind(d);
-    if (!kind) return 0;
-    const int th = kind == 1 ? StemDepth::TH : StemPose::TH;
-    return d->B * ((d->Hd + th - 1) / th) * ((d->Wd + ST_TW - 1) / ST_TW);
-}
-
-bool mcav_try_stem(const mcav_igemm_desc* d, const IgemmParams& p, hipStream_t s) {
-    const int kind = stem_kind(d);
-    if (!kind) return false;
-    const int th = kind == 1 ? StemDepth::TH : StemPose::TH;
+// mcav_igemm's stem family (plan_stem, conv_plan.h)
+void mcav_stem_launch(const IgemmRoute& r, hipStream_t s) {
+    const mcav_igemm_desc* d = r.d;
+    const bool depth = !(r.variant & MCAV_RV_POSE), planar = r.variant & MCAV_RV_PLANAR, lean = r.variant & MCAV_RV_LEAN;
+    const int th = depth ? StemDepth::TH : StemPose::TH;
     const int tiles_x = (d->Wd + ST_TW - 1) / ST_TW, tiles_y = (d->Hd + th - 1) / th;
-    IgemmParams q = p;
+    IgemmParams q = r.p;
     q.groups = 1;                                         // (the statistics rows of a tile are image-major: groups need nothing else)
     const int ntiles = d->B * tiles_x * tiles_y;
-    const bool planar = stem_planar_state(d, kind) == 1;      // (refused descriptors never get here: mcav_igemm checks first)
     const StemPlanar pl = stem_planar_args(d);
-    // The split form of the depth stem: measured 0.189 ms against the fp32 kernel's 0.179 (both with the lean epilogue; 24 x 192 x 640): the stem is
-    // bound by its patch staging and its 189 MB of output stores, which the split kernel's ONE workgroup per CU (125 KB of LDS) has nothing to
-    // overlap with, while its MFMAs take 0.06 instead of 0.10 ms.  OFF under the default mode (mma = 2); mma = 3 (the parity tests) runs it.
-    static const int split_on = MCAV_KNOB_INT("MCAV_STEM_SPLIT", 0);
-    if (kind == 1 && (d->mma == 3 || (d->mma == 2 && split_on))) {
-        static const bool allowed = hipFuncSetAttribute(reinterpret_cast<const void*>(stem7x7s2_split_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                        (int)stem_split_lds_bytes()) == hipSuccess &&
-                                    hipFuncSetAttribute(reinterpret_cast<const void*>(stem7x7s2_split_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                        (int)stem_split_lds_bytes()) == hipSuccess;
+    if (r.variant & MCAV_RV_SPLIT) {                      // (where the device refuses its LDS size: the fp32 kernel below)
+        static const bool allowed = allow_dynamic_lds(stem_split_lds_bytes(), stem7x7s2_split_fwd_kernel<false>, stem7x7s2_split_fwd_kernel<true>);
         if (allowed) {
             const dim3 sgrid(ntiles < 256 ? ntiles : 256);
             if (planar) timed_launch(stem7x7s2_split_fwd_kernel<true>, sgrid, dim3(256), stem_split_lds_bytes(), s, q, d->w_stem, tiles_x, tiles_y, pl);
             else timed_launch(stem7x7s2_split_fwd_kernel<false>, sgrid, dim3(256), stem_split_lds_bytes(), s, q, d->w_stem, tiles_x, tiles_y, pl);
-            return true;
+            return;
         }
     }
     const dim3 grid(ntiles < 512 ? ntiles : 512);         // persistent: 2 per CU
-    const bool lean = (d->tile >> 16) & 1;
-    if (kind == 1 && !lean && planar) timed_launch(stem7x7s2_fwd_kernel<StemDepth, true, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
-    else if (kind == 1 && !lean) timed_launch(stem7x7s2_fwd_kernel<StemDepth, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
-    else if (kind == 1 && planar) timed_launch(stem7x7s2_fwd_kernel<StemDepth, false, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
-    else if (kind == 1) timed_launch(stem7x7s2_fwd_kernel<StemDepth>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
+    if (depth && !lean && planar) timed_launch(stem7x7s2_fwd_kernel<StemDepth, true, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
+    else if (depth && !lean) timed_launch(stem7x7s2_fwd_kernel<StemDepth, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
+    else if (depth && planar) timed_launch(stem7x7s2_fwd_kernel<StemDepth, false, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
+    else if (depth) timed_launch(stem7x7s2_fwd_kernel<StemDepth>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
     else if (planar) timed_launch(stem7x7s2_fwd_kernel<StemPose, false, true>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
     else timed_launch(stem7x7s2_fwd_kernel<StemPose>, grid, dim3(256), 0, s, q, d->w_stem, tiles_x, tiles_y, pl);
-    return true;
 }
 
 MCAV_EXPORT int mcav_pack_stem_weights(const float* w_oihw, int Cout, int Cin, float* packed, void* stream) {
@@ -744,41 +698,15 @@ MCAV_EXPORT int mcav_pack_stem_weights(const float* w_oihw, int Cout, int Cin, f
     return launch_status();
 }
 
-// ---- weight gradient hooks (called by the planner / launcher of conv_igemm.hip, as the halo kernels' are)
-static int stem_wgrad_kind(const mcav_wgrad_desc* d) {
-    if (!d || d->kh != 7 || d->kw != 7 || d->stride != 2 || d->sign != 1 || d->offset != -3 || d->C2 != 0 || d->upm || ((d->tile >> 9) & 1)) return 0;
-    if (d->pad_mode != MCAV_PAD_ZERO || d->up1) return 0;
-    if (d->Hd != (d->Hs - 1) / 2 + 1 || d->Wd != (d->Ws - 1) / 2 + 1 || (d->Cdy & 3) || (d->dy_choff & 3)) return 0;
-    if (d->mode == MCAV_G_SMALLC && d->C1 == 4 && d->Kp == 4 && d->Cout == 64 && d->Cin == 3 && d->Cdy - d->dy_choff >= 64) return 1;
-    if (d->mode == MCAV_G_DIRECT && d->C1 == 16 && d->Kp == 16 && d->Cout == 16 && d->Cin == 9 && d->Cdy - d->dy_choff >= 16) return 2;
-    return 0;
-}
-
-// mcav_wgrad_desc.dy_bn_*: 0 = not set (all zero), 1 = set and launchable (the depth stem, no bias gradient), -1 = set and refused
-int mcav_stem_wgrad_bn(const mcav_wgrad_desc* d) {
-    if (!d) return 0;
-    if (!d->dy_bn_x && !d->dy_bn_gamma && !d->dy_bn_mean && !d->dy_bn_invstd && !d->dy_bn_sums && !d->dy_bn_groups && d->dy_bn_inv_count == 0.f) return 0;
-    if (stem_wgrad_kind(d) != 1 || d->dbias) return -1;      // (conv1 has no bias)
-    if (d->dy_choff != 0 || d->Cdy != 64) return -1;         // the coefficients are indexed by dy's own channel: dy and c1 are exactly the 64 channels
-    if (!d->dy_bn_x || !d->dy_bn_gamma || !d->dy_bn_mean || !d->dy_bn_invstd || !d->dy_bn_sums) return -1;
-    if (d->dy_bn_groups < 1 || d->B % d->dy_bn_groups || !(d->dy_bn_inv_count > 0.f)) return -1;
-    return 1;
-}
-
-int mcav_stem_planar_wgrad(const mcav_wgrad_desc* d) { return d ? stem_planar_state(d, stem_wgrad_kind(d)) : 0; }
-
-int mcav_stem_wgrad_splits(const mcav_wgrad_desc* d) {      // 0 = not applicable, else the number of slab partials (= persistent workgroups)
-    if (!stem_wgrad_kind(d)) return 0;
-    const long tiles = (long)d->B * ((d->Hd + SW_TH - 1) / SW_TH) * ((d->Wd + ST_TW - 1) / ST_TW);
-    return (int)(tiles < 512 ? tiles : 512);
-}
-
-void mcav_stem_wgrad_launch(const mcav_wgrad_desc* d, float* slab, int Ktot, int slabN, int splits, hipStream_t s) {
+// mcav_wgrad's stem family (stem_wgrad_splits, conv_plan.h): writes the slab partials
+void mcav_stem_wgrad_launch(const WgradRoute& r, hipStream_t s) {
+    const mcav_wgrad_desc* d = r.d;
+    float* const slab = r.pl.p.slab;
+    const int Ktot = r.pl.p.Ktot, slabN = r.pl.p.slabN, splits = r.pl.p.splits;
     const int wb = d->dbias != nullptr;
-    const bool planar = mcav_stem_planar_wgrad(d) == 1;
+    const bool planar = r.variant & MCAV_RV_PLANAR, fold = r.variant & MCAV_RV_BN_FOLD;
     const StemPlanar pl = stem_planar_args(d);
     StemWgradBn bn = {};
-    const bool fold = mcav_stem_wgrad_bn(d) == 1;
     if (fold) {
         bn.x = d->dy_bn_x; bn.gamma = d->dy_bn_gamma; bn.mean = d->dy_bn_mean; bn.invstd = d->dy_bn_invstd; bn.sums = d->dy_bn_sums;
         bn.groups = d->dy_bn_groups; bn.inv_count = d->dy_bn_inv_count;
@@ -786,7 +714,7 @@ void mcav_stem_wgrad_launch(const mcav_wgrad_desc* d, float* slab, int Ktot, int
 #define MCAV_STEM_WGRAD_LAUNCH(...)                                                                                                                    \
     timed_launch(stem7x7s2_wgrad_kernel<__VA_ARGS__>, dim3(splits), dim3(256), 0, s, d->x1, d->dy, d->B, d->Hs, d->Ws, d->Hd, d->Wd, d->Cdy, d->dy_choff, \
                  slab, Ktot, slabN, fold ? 0 : wb, bn, pl)
-    if (stem_wgrad_kind(d) == 1) {
+    if (!(r.variant & MCAV_RV_POSE)) {
         if (fold && planar) MCAV_STEM_WGRAD_LAUNCH(3, 4, 64, 4, true, true);
         else if (fold) MCAV_STEM_WGRAD_LAUNCH(3, 4, 64, 4, true, false);
         else if (planar) MCAV_STEM_WGRAD_LAUNCH(3, 4, 64, 4, false, true);

@@ -20,6 +20,12 @@ inline int launch_status() {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// More than 64 KB of dynamic LDS has to be allowed once per kernel: true = every one of `kernels` accepted `bytes`.
+template <class... K>
+inline bool allow_dynamic_lds(size_t bytes, K... kernels) {
+    return ((hipFuncSetAttribute(reinterpret_cast<const void*>(kernels), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess) && ...);
+}
+
 // Tuning and diagnostic switches are COMPILE-TIME.  The shipped library reads no MCAV_* environment variable: every knob below is its
 // default.  An experiment build (`make variant NAME=tune FLAGS=-DMCAV_TUNE_ENV` -> ../mcav/libmcav_depth_tune.so, selected with
 // MCAV_LIB_PATH) reads them from the environment once; the timing-only forms that return WRONG results (conv_bf16.hip MCAV_PATCH_DIAG,

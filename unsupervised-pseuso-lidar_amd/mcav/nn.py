@@ -50,7 +50,32 @@ class WgradReduceItem(ctypes.Structure):
                                    "ci_off", "pre_bx", "red_gx", "red_gy", "pre_first", "red_first", "reserved")]
 
 
+class ConvRoute(ctypes.Structure):
+    """include/mcav_conv.h: mcav_conv_route (which kernel family and form a descriptor takes, as planned)."""
+    _fields_ = [(n, c_i) for n in ("family", "variant", "tile", "mtiles", "ntiles", "workgroups", "splits")] + [("workspace_bytes", c_sz)]
+
+
+# enum mcav_igemm_family / mcav_wgrad_family
+IGEMM_FP32, IGEMM_HALO, IGEMM_STEM, IGEMM_PATCH_F32, IGEMM_BF16_PATCH3, IGEMM_BF16_PATCH2, IGEMM_BF16_PATCH, IGEMM_BF16_TILE = range(8)
+WGRAD_FP32, WGRAD_HALO, WGRAD_STEM, WGRAD_BF16_PATCH, WGRAD_BF16_TILE = range(5)
+# mcav_conv_route.variant bits (MCAV_RV_*)
+RV_ADJ, RV_REFLECT, RV_UPM, RV_PLANAR, RV_LEAN, RV_SPLIT, RV_TMB2, RV_K64, RV_SB4, RV_BN32, RV_TABLE, RV_FAST, RV_BN_FOLD, RV_POSE = (1 << i for i in range(14))
+
+
+ROUTES = None       # tests: a list here makes every conv_fwd / conv_dgrad / conv_wgrad launch append (kind, ConvRoute) -- the route as planned -- before it starts
+
+
+def _launch_igemm(d, kind):
+    if ROUTES is not None:
+        r = ConvRoute()
+        L.check(L.lib().mcav_igemm_route(ctypes.byref(d), ctypes.byref(r)), "mcav_igemm_route(%s)" % kind)
+        ROUTES.append((kind, r))
+    L.check(L.lib().mcav_igemm(ctypes.byref(d), L.stream()), "mcav_igemm(%s)" % kind)
+
+
 L.register({
+    "mcav_igemm_route": (c_i, [ctypes.POINTER(IgemmDesc), ctypes.POINTER(ConvRoute)]),
+    "mcav_wgrad_route": (c_i, [ctypes.POINTER(WgradDesc), ctypes.POINTER(ConvRoute)]),
     "mcav_wgrad_deferred": (c_i, [ctypes.POINTER(WgradDesc), c_p, c_sz, ctypes.POINTER(WgradReduceItem), c_p]),
     "mcav_wgrad_reduce_plan": (c_i, [ctypes.POINTER(WgradReduceItem), c_i, ctypes.POINTER(c_i), ctypes.POINTER(c_i), ctypes.POINTER(c_sz)]),
     "mcav_wgrad_reduce_multi": (c_i, [c_p, c_i, c_i, c_i, c_sz, c_p]),
@@ -543,7 +568,7 @@ def conv_fwd(spec, x1, x2=None, up1=False, act=ACT_NONE, stats=False, tile=0, gr
     abytes = 4.0 * (x1.numel() + (x2.numel() if x2 is not None else 0) + y.numel() + spec.weight.numel())
     with _Timed("fwd", flops, "M=%d N=%d K=%dx%d s%d %dx%d%s" % (B * Hd * Wd, spec.cout, spec.cin, spec.kh * spec.kw, spec.stride, Hd, Wd, _pipe_tag(d)),
                 executed, _planes(d), abytes):
-        L.check(h.mcav_igemm(ctypes.byref(d), L.stream()), "mcav_igemm(fwd)")
+        _launch_igemm(d, "fwd")
     return (y, slab) if stats else y
 
 
@@ -609,7 +634,7 @@ def conv_dgrad(spec, dy, in_shape, n_begin=0, n_count=None, out=None, dact_aux=N
                                                                   " +bn-bwd stats" if slab is not None else "", _pipe_tag(d)), None, _planes(d),
                 4.0 * (B * Hd * Wd * spec.cout + y.numel() * (1 + (dact_aux is not None) + (addend is not None) + (slab is not None))
                        + spec.cout * n_count * spec.kh * spec.kw)):
-        L.check(L.lib().mcav_igemm(ctypes.byref(d), L.stream()), "mcav_igemm(dgrad)")
+        _launch_igemm(d, "dgrad")
     return y if slab is None else (y, slab, slab.shape[0] // bn_stats[1].groups)
 
 
@@ -641,7 +666,7 @@ def _dgrad_upsample_merged(spec, dy, in_shape, c1, dact_aux, dact, addend, tile)
                 "M=%d N=%d K=%dx9 s1 mode2 pool1 (merged 4x4/s2) %dx%d" % (B * Hd * Wd, c1, Cout, Hd, Wd),
                 2.0 * B * (Hl + 2) * (Wl + 2) * spec.cout * c1 * 16, _planes(d),          # 16 taps per low-resolution pixel (incl. the ring) instead of 4 x 9
                 4.0 * (dy.numel() + B * Hl * Wl * c1 * (1 + (dact_aux is not None) + (addend is not None)) + spec.cout * c1 * 9)):
-        L.check(L.lib().mcav_igemm(ctypes.byref(d), L.stream()), "mcav_igemm(dgrad, merged upsample)")
+        _launch_igemm(d, "dgrad, merged upsample")
         y = empty((B, Hl, Wl, c1), dy)
         L.check(L.lib().mcav_upsample_adj_fold(P(tmp), B, Hl, Wl, c1, P(dact_aux), dact, P(addend), P(y), L.stream()), "mcav_upsample_adj_fold")
     return y
@@ -900,7 +925,10 @@ def launch_wgrad(d, tensors, flops=0.0, tag="", executed=None):
     nbytes = h.mcav_wgrad_workspace_bytes(ctypes.byref(d))
     if nbytes == 0:
         raise L.MCAVError("mcav_wgrad: invalid descriptor")
-
+    if ROUTES is not None:
+        r = ConvRoute()
+        L.check(h.mcav_wgrad_route(ctypes.byref(d), ctypes.byref(r)), "mcav_wgrad_route")
+        ROUTES.append(("wgrad", r))
     dev = tensors[0].device
     planes = _planes(d) if (d.mma and h.mcav_wgrad_uses_bf16(ctypes.byref(d))) else 0
     global LAST_WGRAD_PLANES
