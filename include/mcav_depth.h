@@ -112,6 +112,15 @@ int mcav_warp_loss_stereo_fwd_bwd(const float* tgt, const float* ref0, const flo
                                   unsigned char* selection, size_t selection_bytes,
                                   const float* stereo, const float* stereo_baseline);
 
+/* Query, nothing is launched: the grid a launch of the fused L1 kernels would use.  Every sample gets G0 pass-0 and G1 pass-1 workgroups
+ * (grid = (G0 + G1, B)); workgroup g of a pass walks the 32 x 16 pixel tiles g, g + G, ... of its sample.  The instantiation is the one the
+ * entries above pick: the MCAV_WL_MIN_REPROJ / MCAV_WL_AUTOMASK bits of flags, and stereo != 0 for mcav_warp_loss_stereo_fwd_bwd's kernels.
+ * slots > 0 plans for that many resident workgroups and needs no device; slots = 0 asks the runtime (CUs x workgroups per CU of that
+ * instantiation) exactly as the launch does.  The launch and this query run one planner.
+ * Returns MCAV_E_INVALID where the launch would (B <= 0, B > 4095, H < 3, W < 3, unknown flag bits), for a null G0 / G1 or slots < 0, and
+ * for MCAV_WL_SSIM, whose kernels use one workgroup per tile. */
+int mcav_warp_loss_l1_grid(int B, int H, int W, unsigned flags, int stereo, int slots, int* G0, int* G1);
+
 /* DIAGNOSTIC twin of mcav_warp_loss_fwd_bwd (upstream (1,1)): the same kernel bodies with a per-pixel dump, used by
  * tests/flip_finder.py to NAME the pixels at which an fp32 evaluation takes another bilinear cell / L1 sign than float64 does
  * (losses.py:183-240 is only piecewise smooth).  taps: [B][3 warps][7][H][W] = { ix, iy (un-normalised sampling position, source pixels),
@@ -141,7 +150,8 @@ int mcav_project(const float* points, const void* K, const float* Tcw, int B, in
                  float* grid, void* stream);
 
 /* transformation_from_parameters / rot_from_axisangle / get_translation_matrix (pose_geometry.py:124-199):
- * pose [B,6] = (axis-angle, translation) -> T [B,4,4] = Trans @ Rot, or its rigid inverse. */
+ * pose [B,6] = (axis-angle, translation) -> T [B,4,4] = Trans @ Rot, or its rigid inverse.  float32 as the reference; the inverse's
+ * translation -R^T t is formed in float64 and rounded once (in float32 it inherits the rotation's absolute error times t). */
 int mcav_pose_to_matrix(const float* pose, int B, int invert, float* T, void* stream);
 /* invert_pose (pose_geometry.py:110-115): T [B,4,4] rigid -> [R^T | -R^T t]. */
 int mcav_invert_pose(const float* T, int B, float* Tinv, void* stream);
@@ -180,7 +190,8 @@ int mcav_depth_pyramid_bwd(const mcav_pyr_level* levels, int nlevels, int B, int
 int mcav_ssim_fwd(const float* x, const float* y, int N, int H, int W, float C1, float C2, float* out, void* stream);
 
 /* Losses.smooth_loss for ONE scale (losses.py:242-260): depth [B,1,H,W]; loss_accum[0] += weight * term,
- * d_depth (+)= upstream[0] * weight * d term.  accumulate != 0 adds into d_depth. */
+ * d_depth (+)= upstream[0] * weight * d term.  accumulate != 0 adds into d_depth.  The signs of a pixel's ten terms are summed exactly
+ * and weighted in float64: each gradient element is rounded once. */
 size_t mcav_smooth_workspace_bytes(int B, int H, int W);
 int mcav_smooth_loss_fwd_bwd(const float* depth, int B, int H, int W, float weight, const float* upstream,
                              float* loss_accum, float* d_depth, int accumulate,

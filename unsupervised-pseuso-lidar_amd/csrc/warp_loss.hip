@@ -521,11 +521,29 @@ __global__ __launch_bounds__(256) void project_kernel(const float* pts, const vo
     grid[((size_t)b * plane + pix) * 2 + 1] = ((c1 / z) / (float)(H - 1) - 0.5f) * 2.0f;
 }
 
+// The translation of the rigid inverse, t' = -R^T t, with Rodrigues (+1e-7f) in float64 and ONE rounding at the end.  Formed from the
+// float32 rotation it inherits that rotation's absolute error (up to 8 u per entry near a half turn) times t, which is larger than t'
+// itself wherever a column of R is small; this way every entry is within one rounding of the float64 value.  The standalone entry only:
+// the fused kernels keep pose_to_Rt (csrc/warp_math.h), the reference's float32 chain.
+__device__ __forceinline__ void inverse_translation_f64(const float* pose, float* t) {
+    const double vx = pose[0], vy = pose[1], vz = pose[2];
+    const double angle = sqrt(vx * vx + vy * vy + vz * vz);
+    const double inv = 1.0 / (angle + (double)1e-7f);
+    const double x = vx * inv, y = vy * inv, z = vz * inv;
+    const double ca = cos(angle), sa = sin(angle), C = 1.0 - ca;
+    const double R0[9] = {x * x * C + ca, x * y * C - z * sa, z * x * C + y * sa,
+                          x * y * C + z * sa, y * y * C + ca, y * z * C - x * sa,
+                          z * x * C - y * sa, y * z * C + x * sa, z * z * C + ca};
+    for (int i = 0; i < 3; ++i)
+        t[i] = (float)(-(R0[0 * 3 + i] * (double)pose[3] + R0[1 * 3 + i] * (double)pose[4] + R0[2 * 3 + i] * (double)pose[5]));
+}
+
 __global__ void pose_to_matrix_kernel(const float* pose, int B, int invert, float* T) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     float R[9], t[3];
     pose_to_Rt(pose + (size_t)b * 6, invert != 0, R, t);
+    if (invert) inverse_translation_f64(pose + (size_t)b * 6, t);
     float* o = T + (size_t)b * 16;
     for (int i = 0; i < 3; ++i) {
         for (int j = 0; j < 3; ++j) o[i * 4 + j] = R[i * 3 + j];
@@ -612,12 +630,24 @@ __global__ __launch_bounds__(256) void smooth_kernel(const float* depth, int B, 
         const float cxx = weight / (float)((size_t)B * H * (W - 2));
         const float cyy = weight / (float)((size_t)B * (H - 2) * W);
         const float cxy = 2.0f * weight / (float)((size_t)B * (H - 1) * (W - 1));
+        auto DD = [&](int dy, int dx) { return sD[cy + dy][cx + dx]; };
         float gs = 0.f, ls = 0.f;
-        smooth_terms([&](int dy, int dx) { return sD[cy + dy][cx + dx]; }, x, y, H, W, cxx, cyy, cxy, ls, gs);
+        smooth_terms(DD, x, y, H, W, cxx, cyy, cxy, ls, gs);
         acc[0] = ls;
-        const float g = upstream ? upstream[0] : 1.0f;
+        // The gradient is a sum of ten signed coefficients, 7 to 8 times the largest in magnitude: in float32 the rounding of weight / n and
+        // of nine additions costs up to 19 u of the largest coefficient (measured).  The signs of each group are summed as small integers
+        // (exact) and weighted in float64, so the element is rounded once.
+        float nx = 0.f, ny = 0.f, nxy = 0.f, unused = 0.f;
+        smooth_terms(DD, x, y, H, W, 1.0f, 0.0f, 0.0f, unused, nx);
+        smooth_terms(DD, x, y, H, W, 0.0f, 1.0f, 0.0f, unused, ny);
+        smooth_terms(DD, x, y, H, W, 0.0f, 0.0f, 1.0f, unused, nxy);
+        const double w = (double)weight;
+        const double gsd = (double)nx * (w / (double)((size_t)B * H * (W - 2))) + (double)ny * (w / (double)((size_t)B * (H - 2) * W)) +
+                           (double)nxy * (2.0 * w / (double)((size_t)B * (H - 1) * (W - 1)));
+        const double g = upstream ? (double)upstream[0] : 1.0;
         const size_t o = (size_t)b * plane + (size_t)y * W + x;
-        d_depth[o] = (accumulate ? d_depth[o] : 0.f) + g * gs;
+        d_depth[o] = (float)((accumulate ? (double)d_depth[o] : 0.0) + g * gsd);
+        (void)gs;
     }
     const int nblk = gridDim.x * gridDim.y * gridDim.z;
     const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
@@ -882,6 +912,32 @@ MCAV_EXPORT int mcav_warp_loss_stereo_fwd_bwd(const float* tgt, const float* ref
                                     stereo_baseline);
     if (rc != MCAV_OK || mode != 0 || !selection) return rc;
     return hipMemsetAsync(selection, 0, sel_bytes, as_stream(stream)) == hipSuccess ? MCAV_OK : MCAV_E_LAUNCH;      // plain: every warp kept
+}
+
+// resident workgroups of the fused L1 instantiation of (masked mode, stereo): the same cached answers the launches above take
+static int l1_slots_of(unsigned mode, bool stereo) {
+    if (stereo) {
+        if (mode == (WL_M_MIN | WL_M_AUTO)) return l1_stereo_slots<WL_M_MIN | WL_M_AUTO>();
+        if (mode == WL_M_MIN) return l1_stereo_slots<WL_M_MIN>();
+        if (mode == WL_M_AUTO) return l1_stereo_slots<WL_M_AUTO>();
+        return l1_stereo_slots<0>();
+    }
+    if (mode == (WL_M_MIN | WL_M_AUTO)) return l1_slots<WL_M_MIN | WL_M_AUTO>();
+    if (mode == WL_M_MIN) return l1_slots<WL_M_MIN>();
+    if (mode == WL_M_AUTO) return l1_slots<WL_M_AUTO>();
+    return l1_slots<0>();
+}
+
+// The planner of the fused L1 launches as a query: l1_grid itself, nothing launched (the precedent is mcav_igemm_route).
+MCAV_EXPORT int mcav_warp_loss_l1_grid(int B, int H, int W, unsigned flags, int stereo, int slots, int* G0, int* G1) {
+    constexpr unsigned known = MCAV_WL_K_F64 | MCAV_WL_SKIP_IF_UNIT | MCAV_WL_NO_SMOOTH | MCAV_WL_INPUT_DEPTH | MCAV_WL_SSIM |
+                               MCAV_WL_MIN_REPROJ | MCAV_WL_AUTOMASK;
+    if (!G0 || !G1 || slots < 0 || (flags & ~known) || (flags & MCAV_WL_SSIM)) return MCAV_E_INVALID;
+    if (B <= 0 || H < 3 || W < 3 || B > WL_MAX_B) return MCAV_E_INVALID;
+    const unsigned mode = ((flags & MCAV_WL_MIN_REPROJ) ? WL_M_MIN : 0u) | ((flags & MCAV_WL_AUTOMASK) ? WL_M_AUTO : 0u);
+    if (slots == 0) slots = l1_slots_of(mode, stereo != 0);
+    l1_grid(B, H, W, slots, *G0, *G1, stereo != 0);
+    return MCAV_OK;
 }
 
 // Diagnostic twin of mcav_warp_loss_fwd_bwd: the same kernel bodies instantiated with their per-pixel dump on.
