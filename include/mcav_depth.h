@@ -378,6 +378,37 @@ int mcav_pl_batch_project_scaled(const float* m, int B, int h, int w, int Hg, in
                                  float scale, const float* scales, double max_height, double max_depth, int sparsity, int flags,
                                  float* cloud, size_t capacity_points, int* offsets, void* workspace, size_t workspace_bytes,
                                  void* stream);
+/* mcav_pl_batch_project_scaled that also records where every row came from: pixels (device int32 [capacity_points], not NULL) gets
+ * pixels[o] = r * Wg + c, the pixel of its image's padded grid that became row o (the image follows from offsets), in the dense form, with
+ * sparsity and in the beam form.  Rows at and beyond capacity_points are not written.  Same kernels, launches and workspace; cloud and
+ * offsets are mcav_pl_batch_project_scaled's, bit for bit. */
+int mcav_pl_batch_project_indexed(const float* m, int B, int h, int w, int Hg, int Wg, const int* sizes, const double* calib,
+                                  const float* intensity, const double* elev, const double* azim, int n_beams, int n_azimuth,
+                                  float scale, const float* scales, double max_height, double max_depth, int sparsity, int flags,
+                                  float* cloud, size_t capacity_points, int* offsets, int* pixels, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+/* The backward of mcav_pl_batch_project_indexed: the gradient of the cloud rows -> the gradient of the plane m.  The selection (which
+ * pixels became rows) is piecewise constant and has no gradient; scale, scales, intensity and the calibration get none.  The definition is
+ * tests/pl_bwd_ref.py; the arithmetic is csrc/pl_bwd_math.h.  m, sizes, calib, scale, scales, flags: the forward's; pixels, offsets: what it
+ * left; d_points: device [capacity_points, 4] float32, 16-byte aligned (column 3, the intensity, is ignored; rows at and beyond
+ * min(offsets[B], capacity_points) are never read); d_m: device [B, h, w] float32, every element written.
+ *   a) G [B, Hg, Wg] = +0.0 (a memset node), then for row o of image b at (r, c) = pixels[o]: v and s_b as the forward has them, in float64
+ *      a_j = (((c - cu) / fu) ti[j][0] + ((r - cv) / fv) ti[j][1]) + ti[j][2], g_d = (g0 a_0 + g1 a_1) + g2 a_2,
+ *      slope = ((-10 s_b) u) u with u = 1 / (10 v + 0.01), or s_b with MCAV_PLB_INPUT_DEPTH; G[b][r][c] = float32(g_d slope).  A pixel owns
+ *      at most one row in every form.  A row whose pixel lies outside its image is skipped.
+ *   b) d_m[b][y][x] = the float64 sum, rounded once, over the outputs (r, c) of image b whose taps touch (y, x), in ascending (r, c)
+ *      order, of (wy(r, y) wx(c, x)) G[b][r][c] with the forward's float32 weights 1 - l and l (both added in float32 when the taps coincide
+ *      at the last source); the windows by bisection over csrc/eval_math.h's bilinear_axis itself.  (h, w) == (Hb, Wb): G[b][y][x].  An image
+ *      whose s_b is not finite and positive: +0.0.
+ * No atomics: bit-identical from run to run.  A memset and 2 launches; no host synchronisation, allocation or copy: the call can be
+ * captured.  Workspace (mcav_pl_batch_project_bwd_workspace_bytes, 0 for sizes that are refused): the plane G, 4 B Hg Wg bytes rounded up
+ * to 256, 4-byte aligned; no zero-fill needed.
+ * Returns MCAV_E_INVALID for a null pointer (scales may be NULL), a non-positive size, B * Hg * Wg or B * h * w >= 2^31, a NaN scale, a
+ * misaligned d_points or workspace or unknown flag bits, MCAV_E_WORKSPACE for a short workspace; nothing is launched then. */
+size_t mcav_pl_batch_project_bwd_workspace_bytes(int B, int Hg, int Wg);
+int mcav_pl_batch_project_bwd(const float* d_points, size_t capacity_points, const int* pixels, const int* offsets, const float* m, int B,
+                              int h, int w, int Hg, int Wg, const int* sizes, const double* calib, float scale, const float* scales,
+                              int flags, float* d_m, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Metric scale of a monocular prediction from the ground plane (DNet's dense geometrical constraint, Xue et al., IROS 2020): per image, a
  * surface normal per pixel from the back-projected depth, the pixels whose normal points along the camera's "down" axis, and
@@ -443,6 +474,30 @@ size_t mcav_pillarize_workspace_bytes(int B, long long n_max, int ny, int nx);
 int mcav_pillarize(const float* points, const int* offsets, int B, long long n_max, float x0, float y0, float z0, float z1, float vx,
                    float vy, int nx, int ny, int max_points, int flags, float* voxels, int* coords, int* num_points, long long capacity,
                    int* pillar_offsets, void* workspace, size_t workspace_bytes, void* stream);
+/* mcav_pillarize that also records which cloud row every slot holds: slot_points (device int32 [capacity, max_points], not NULL) gets the
+ * row's index in `points`, -1 in the zero-padded slots.  Rows at and beyond min(pillar_offsets[B], capacity) are not written.  Same
+ * kernels, launches and workspace; every other output is mcav_pillarize's, bit for bit. */
+int mcav_pillarize_indexed(const float* points, const int* offsets, int B, long long n_max, float x0, float y0, float z0, float z1, float vx,
+                           float vy, int nx, int ny, int max_points, int flags, float* voxels, int* coords, int* num_points,
+                           long long capacity, int* pillar_offsets, int* slot_points, void* workspace, size_t workspace_bytes,
+                           void* stream);
+/* The backward of mcav_pillarize_indexed: the gradient of the voxels -> the gradient of the cloud rows.  Which row lands in which slot is
+ * piecewise constant and has no gradient.  The definition is tests/pl_bwd_ref.py; the arithmetic is csrc/pl_bwd_math.h.
+ * d_voxels: device [capacity, max_points, C] float32 (C = 9 with MCAV_PILLAR_DECORATE, else 4; rows at and beyond
+ * P = min(pillar_offsets[B], capacity) are never read); slot_points, num_points, pillar_offsets: what the forward left;
+ * d_points: device [n_max, 4] float32, 16-byte aligned, every row written.  Slot k < count = num_points[p] of pillar p holding row i:
+ *   C = 4   d_points[i][c] = g[k][c]
+ *   C = 9   d_points[i][0] = float32((((double)g[k][0] + g[k][4]) + g[k][7]) - S4 / count), S4 = the float64 sum of g[j][4] over
+ *           j = 0 .. count - 1 in slot order from +0 (the mean's derivative; the cell's centre is a constant); y from columns 1, 5, 8 and
+ *           S5; z from columns 2, 6 and S6 (no centre column); column 3 passes through.
+ * A row is in at most one slot: no atomics, the same bytes from run to run.  A row that no slot holds (beyond the first max_points of its
+ * cell, outside the grid, in a pillar beyond the capacity) is +0.0.  A memset and one launch, one wavefront per pillar; no workspace, no
+ * host synchronisation: the call can be captured.
+ * Returns MCAV_E_INVALID for a null pointer, B <= 0, B > 65535, n_max < 0, n_max >= 2^31, capacity < 0, max_points outside [1, 64],
+ * unknown flag bits, a d_points address that is no multiple of 16 or a d_voxels address that is no multiple of 4; nothing is launched
+ * then. */
+int mcav_pillarize_bwd(const float* d_voxels, const int* slot_points, const int* num_points, const int* pillar_offsets, int B,
+                       long long capacity, int max_points, int flags, float* d_points, long long n_max, void* stream);
 
 /* Pillars -> pillar features -> bird's-eye-view pseudo-image, the first layers of a LiDAR 3-D detector (PointPillars / SECOND / OpenPCDet:
  * PillarVFE's Linear + BatchNorm1d + ReLU + max over the pillar's points with the BatchNorm folded into the layer, then

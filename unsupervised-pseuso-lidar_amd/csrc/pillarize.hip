@@ -9,6 +9,8 @@
 //   gather  : per pillar, the max_points smallest indices of its segment in ascending order (64 at a time, each entry ranked among the
 //             kept set and the chunk), the points, the float64 means in slot order, the row block through LDS with 16-byte stores
 // Integer atomics only, nothing returns to the host, no allocation: the call can be captured, and two runs give the same bytes.
+// mcav_pillarize_indexed is the same sequence with one more store in the gather: the cloud row in every slot (-1 in the padding), which is
+// all the backward (pl_bwd.hip) needs to know of the selection.
 #include <limits.h>
 
 #include "block_ops.h"
@@ -127,7 +129,7 @@ __global__ __launch_bounds__(THREADS) void pil_fill_kernel(const int2* rec, cons
 template <bool DECORATE>
 __global__ __launch_bounds__(64) void pil_gather_kernel(const f32x4* points, const unsigned* cells, const int* index, const int* pillar_cell,
                                                         const int* pillar_offsets, int B, Grid g, unsigned per_image, int N, float* voxels,
-                                                        int4* coords, int* num_points, size_t capacity) {
+                                                        int4* coords, int* num_points, size_t capacity, int* slot_points) {
     constexpr int C = DECORATE ? COLS_DECORATED : COLS_PLAIN;
     __shared__ int kept[2][MAX_POINTS];
     __shared__ int chunk[64];
@@ -183,6 +185,7 @@ __global__ __launch_bounds__(64) void pil_gather_kernel(const f32x4* points, con
         } else {
             for (int e = lane; e < total; e += 64) out[e] = tile[e];
         }
+        if (slot_points && lane < N) slot_points[r * (size_t)N + lane] = lane < k ? kept[cur][lane] : -1;       // mcav_pillarize_indexed
         if (lane == 0) {
             coords[r] = make_int4(b, 0, iy, ix);
             num_points[r] = k;
@@ -224,9 +227,10 @@ MCAV_EXPORT size_t mcav_pillarize_workspace_bytes(int B, long long n_max, int ny
     return pil::layout(B, n_max, ny, nx, l) ? l.total : 0;
 }
 
-MCAV_EXPORT int mcav_pillarize(const float* points, const int* offsets, int B, long long n_max, float x0, float y0, float z0, float z1, float vx,
-                               float vy, int nx, int ny, int max_points, int flags, float* voxels, int* coords, int* num_points,
-                               long long capacity, int* pillar_offsets, void* workspace, size_t workspace_bytes, void* stream) {
+// both entries' body; slot_points: null, or device int [capacity, max_points]
+static int pillarize(const float* points, const int* offsets, int B, long long n_max, float x0, float y0, float z0, float z1, float vx, float vy,
+                     int nx, int ny, int max_points, int flags, float* voxels, int* coords, int* num_points, long long capacity,
+                     int* pillar_offsets, int* slot_points, void* workspace, size_t workspace_bytes, void* stream) {
     if (!points || !offsets || !voxels || !coords || !num_points || !pillar_offsets || !workspace) return MCAV_E_INVALID;
     if (max_points < 1 || max_points > pil::MAX_POINTS || capacity < 0 || (flags & ~MCAV_PILLAR_DECORATE)) return MCAV_E_INVALID;
     const pil::Grid g{x0, y0, z0, z1, vx, vy, nx, ny};
@@ -262,10 +266,26 @@ MCAV_EXPORT int mcav_pillarize(const float* points, const int* offsets, int B, l
         const unsigned blocks = (unsigned)(rows < (size_t)pil::GATHER_BLOCKS ? rows : (size_t)pil::GATHER_BLOCKS);
         if (flags & MCAV_PILLAR_DECORATE)
             pil::pil_gather_kernel<true><<<blocks, 64, 0, s>>>(pts, cells, index, pillar_cell, pillar_offsets, B, g, per_image, max_points,
-                                                               voxels, reinterpret_cast<int4*>(coords), num_points, (size_t)capacity);
+                                                               voxels, reinterpret_cast<int4*>(coords), num_points, (size_t)capacity, slot_points);
         else
             pil::pil_gather_kernel<false><<<blocks, 64, 0, s>>>(pts, cells, index, pillar_cell, pillar_offsets, B, g, per_image, max_points,
-                                                                voxels, reinterpret_cast<int4*>(coords), num_points, (size_t)capacity);
+                                                                voxels, reinterpret_cast<int4*>(coords), num_points, (size_t)capacity, slot_points);
     }
     return launch_status();
+}
+
+MCAV_EXPORT int mcav_pillarize(const float* points, const int* offsets, int B, long long n_max, float x0, float y0, float z0, float z1, float vx,
+                               float vy, int nx, int ny, int max_points, int flags, float* voxels, int* coords, int* num_points,
+                               long long capacity, int* pillar_offsets, void* workspace, size_t workspace_bytes, void* stream) {
+    return pillarize(points, offsets, B, n_max, x0, y0, z0, z1, vx, vy, nx, ny, max_points, flags, voxels, coords, num_points, capacity,
+                     pillar_offsets, nullptr, workspace, workspace_bytes, stream);
+}
+
+MCAV_EXPORT int mcav_pillarize_indexed(const float* points, const int* offsets, int B, long long n_max, float x0, float y0, float z0, float z1,
+                                       float vx, float vy, int nx, int ny, int max_points, int flags, float* voxels, int* coords,
+                                       int* num_points, long long capacity, int* pillar_offsets, int* slot_points, void* workspace,
+                                       size_t workspace_bytes, void* stream) {
+    if (!slot_points) return MCAV_E_INVALID;
+    return pillarize(points, offsets, B, n_max, x0, y0, z0, z1, vx, vy, nx, ny, max_points, flags, voxels, coords, num_points, capacity,
+                     pillar_offsets, slot_points, workspace, workspace_bytes, stream);
 }

@@ -6,6 +6,8 @@
 //           same count / scan / scatter over the cells
 // Every pass recomputes the point instead of storing it (4 B read per network pixel, 16 B written per point); nothing returns to the host,
 // no copy from the host and no allocation: the call can be captured.  No float atomics: bit-identical from run to run.
+// mcav_pl_batch_project_indexed is the same sequence with one more store in the scatter: the pixel behind every row, which is all the
+// backward (pl_bwd.hip) needs to know of the selection.
 #include "block_ops.h"
 #include "pl_math.h"
 
@@ -102,8 +104,9 @@ __global__ __launch_bounds__(1024) void plb_scan_kernel(unsigned* counts, int nb
     }
 }
 
+// pixels (or null): pixels[o] = the pixel of the image's padded grid that became row o (mcav_pl_batch_project_indexed)
 __global__ __launch_bounds__(THREADS) void plb_scatter_kernel(Args a, const unsigned* scan, const int* offsets, unsigned step, f32x4* cloud,
-                                                              size_t capacity) {
+                                                              size_t capacity, int* pixels) {
     __shared__ unsigned wsum[THREADS / 64];
     const int b = blockIdx.x / a.per_image;
     const unsigned p = (unsigned)(blockIdx.x - b * a.per_image) * THREADS + threadIdx.x;
@@ -118,6 +121,7 @@ __global__ __launch_bounds__(THREADS) void plb_scatter_kernel(Args a, const unsi
             f32x4 row;
             row[0] = (float)q[0]; row[1] = (float)q[1]; row[2] = (float)q[2]; row[3] = pixel_intensity(a, b, r, c);
             cloud[o] = row;
+            if (pixels) pixels[o] = (int)p;
         }
     }
 }
@@ -152,7 +156,7 @@ __global__ __launch_bounds__(THREADS) void plb_cell_count_kernel(Args a, const u
 }
 
 __global__ __launch_bounds__(THREADS) void plb_cell_scatter_kernel(Args a, const unsigned long long* cells, int per_cells, const unsigned* scan,
-                                                                   f32x4* cloud, size_t capacity) {
+                                                                   f32x4* cloud, size_t capacity, int* pixels) {
     __shared__ unsigned wsum[THREADS / 64];
     int b;
     unsigned long long word = EMPTY_CELL;
@@ -166,6 +170,7 @@ __global__ __launch_bounds__(THREADS) void plb_cell_scatter_kernel(Args a, const
             f32x4 row;
             row[0] = (float)q[0]; row[1] = (float)q[1]; row[2] = (float)q[2]; row[3] = pixel_intensity(a, b, r, c);
             cloud[o] = row;
+            if (pixels) pixels[o] = r * a.Wg + c;
         }
     }
 }
@@ -203,11 +208,11 @@ MCAV_EXPORT int mcav_pl_beam_tables_check(const double* elev_host, int n_beams, 
     return plb::table_ok(elev_host, n_beams) && plb::table_ok(azim_host, n_azimuth) ? MCAV_OK : MCAV_E_INVALID;
 }
 
-MCAV_EXPORT int mcav_pl_batch_project_scaled(const float* m, int B, int h, int w, int Hg, int Wg, const int* sizes, const double* calib,
-                                             const float* intensity, const double* elev, const double* azim, int n_beams, int n_azimuth,
-                                             float scale, const float* scales, double max_height, double max_depth, int sparsity, int flags,
-                                             float* cloud, size_t capacity_points, int* offsets, void* workspace, size_t workspace_bytes,
-                                             void* stream) {
+// the three entries' body; pixels: null, or device int [capacity_points]
+static int project(const float* m, int B, int h, int w, int Hg, int Wg, const int* sizes, const double* calib, const float* intensity,
+                   const double* elev, const double* azim, int n_beams, int n_azimuth, float scale, const float* scales, double max_height,
+                   double max_depth, int sparsity, int flags, float* cloud, size_t capacity_points, int* offsets, int* pixels, void* workspace,
+                   size_t workspace_bytes, void* stream) {
     if (!m || !sizes || !calib || !cloud || !offsets || !workspace || h <= 0 || w <= 0 || sparsity < 0) return MCAV_E_INVALID;
     if (flags & ~MCAV_PLB_INPUT_DEPTH) return MCAV_E_INVALID;
     if ((elev != nullptr) != (azim != nullptr) || (elev != nullptr) != (n_beams > 0)) return MCAV_E_INVALID;
@@ -238,7 +243,7 @@ MCAV_EXPORT int mcav_pl_batch_project_scaled(const float* m, int B, int h, int w
         const unsigned step = sparsity > 0 ? (unsigned)sparsity : 1u;
         plb::plb_count_kernel<<<npix, plb::THREADS, 0, s>>>(a, counts);
         plb::plb_scan_kernel<<<1, 1024, 0, s>>>(counts, npix, l.per_image, B, step, offsets);
-        plb::plb_scatter_kernel<<<npix, plb::THREADS, 0, s>>>(a, counts, offsets, step, out, capacity_points);
+        plb::plb_scatter_kernel<<<npix, plb::THREADS, 0, s>>>(a, counts, offsets, step, out, capacity_points, pixels);
         return launch_status();
     }
     const int ncell = B * l.per_cells;
@@ -246,8 +251,27 @@ MCAV_EXPORT int mcav_pl_batch_project_scaled(const float* m, int B, int h, int w
     plb::plb_bin_kernel<<<npix, plb::THREADS, 0, s>>>(a, cells);
     plb::plb_cell_count_kernel<<<ncell, plb::THREADS, 0, s>>>(a, cells, l.per_cells, counts);
     plb::plb_scan_kernel<<<1, 1024, 0, s>>>(counts, ncell, l.per_cells, B, 1u, offsets);
-    plb::plb_cell_scatter_kernel<<<ncell, plb::THREADS, 0, s>>>(a, cells, l.per_cells, counts, out, capacity_points);
+    plb::plb_cell_scatter_kernel<<<ncell, plb::THREADS, 0, s>>>(a, cells, l.per_cells, counts, out, capacity_points, pixels);
     return launch_status();
+}
+
+MCAV_EXPORT int mcav_pl_batch_project_scaled(const float* m, int B, int h, int w, int Hg, int Wg, const int* sizes, const double* calib,
+                                             const float* intensity, const double* elev, const double* azim, int n_beams, int n_azimuth,
+                                             float scale, const float* scales, double max_height, double max_depth, int sparsity, int flags,
+                                             float* cloud, size_t capacity_points, int* offsets, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
+    return project(m, B, h, w, Hg, Wg, sizes, calib, intensity, elev, azim, n_beams, n_azimuth, scale, scales, max_height, max_depth, sparsity,
+                   flags, cloud, capacity_points, offsets, nullptr, workspace, workspace_bytes, stream);
+}
+
+MCAV_EXPORT int mcav_pl_batch_project_indexed(const float* m, int B, int h, int w, int Hg, int Wg, const int* sizes, const double* calib,
+                                              const float* intensity, const double* elev, const double* azim, int n_beams, int n_azimuth,
+                                              float scale, const float* scales, double max_height, double max_depth, int sparsity, int flags,
+                                              float* cloud, size_t capacity_points, int* offsets, int* pixels, void* workspace,
+                                              size_t workspace_bytes, void* stream) {
+    if (!pixels) return MCAV_E_INVALID;
+    return project(m, B, h, w, Hg, Wg, sizes, calib, intensity, elev, azim, n_beams, n_azimuth, scale, scales, max_height, max_depth, sparsity,
+                   flags, cloud, capacity_points, offsets, pixels, workspace, workspace_bytes, stream);
 }
 
 MCAV_EXPORT int mcav_pl_batch_project(const float* m, int B, int h, int w, int Hg, int Wg, const int* sizes, const double* calib,

@@ -21,12 +21,19 @@ OpenPCDet): a `PillarBatch` of voxels [P, N, C], coords [P, 4] = (batch, z, y, x
 of every non-empty cell in cloud order (mcav_pillarize; the definition is tests/pillar_ref.py).  Still nothing is read back.
 `PillarBatch.pseudo_image(net)` takes them through a detector's pillar feature net into its bird's-eye-view canvas (PillarFeatureNet.py).
 
+The chain disparity -> cloud -> pillars -> canvas is differentiable down to the disparity (End-to-End Pseudo-LiDAR): with grad mode on and
+a plane that requires a gradient `project_batch` and `pillarize` are nodes of the autograd graph whose backwards are HIP kernels
+(mcav_pl_batch_project_bwd, mcav_pillarize_bwd; the definition is tests/pl_bwd_ref.py).  The forwards then record their selection
+(`CloudBatch.pixels`, `PillarBatch.slot_points`; `provenance=True` does so without a gradient), which is all the backwards need: selection
+itself is piecewise constant.  `project_batch_backward` / `pillarize_backward` are the raw calls.
+
 `gdc(depth, sparse, K)` is Pseudo-LiDAR++'s graph-based depth correction: a few exact LiDAR depths (a 4-beam scanner's, as a sparse map
 on the prediction's grid: geometry.velodyne.sparse_maps) are propagated over the predicted depth map along a windowed KNN graph of its
 back-projected pixels, keeping the predicted local shape (mcav_gdc_graph, mcav_gdc_solve; the definition is tests/gdc_ref.py).  The
 corrected map goes into project_batch(input="depth").
 """
 import ctypes
+import weakref
 
 import numpy as np
 import torch
@@ -42,12 +49,20 @@ L.register({
                                       L.c_p, L.c_sz, L.c_p, L.c_p, L.c_sz, L.c_p]),
     "mcav_pl_batch_project_scaled": (L.c_i, [L.c_p] + [L.c_i] * 5 + [L.c_p] * 5 + [L.c_i, L.c_i, L.c_f, L.c_p, ctypes.c_double, ctypes.c_double,
                                              L.c_i, L.c_i, L.c_p, L.c_sz, L.c_p, L.c_p, L.c_sz, L.c_p]),
+    "mcav_pl_batch_project_indexed": (L.c_i, [L.c_p] + [L.c_i] * 5 + [L.c_p] * 5 + [L.c_i, L.c_i, L.c_f, L.c_p, ctypes.c_double, ctypes.c_double,
+                                              L.c_i, L.c_i, L.c_p, L.c_sz, L.c_p, L.c_p, L.c_p, L.c_sz, L.c_p]),
+    "mcav_pl_batch_project_bwd_workspace_bytes": (L.c_sz, [L.c_i] * 3),
+    "mcav_pl_batch_project_bwd": (L.c_i, [L.c_p, L.c_sz, L.c_p, L.c_p, L.c_p] + [L.c_i] * 5 + [L.c_p, L.c_p, L.c_f, L.c_p, L.c_i, L.c_p, L.c_p,
+                                          L.c_sz, L.c_p]),
     "mcav_ground_scale_workspace_bytes": (L.c_sz, [L.c_i] * 3),
     "mcav_ground_scale": (L.c_i, [L.c_p, L.c_i, L.c_i, L.c_i, L.c_p, L.c_p, L.c_p, L.c_f, L.c_f, L.c_i, L.c_f, L.c_i, L.c_p, L.c_p, L.c_p,
                                   L.c_sz, L.c_p]),
     "mcav_pillarize_workspace_bytes": (L.c_sz, [L.c_i, ctypes.c_longlong, L.c_i, L.c_i]),
     "mcav_pillarize": (L.c_i, [L.c_p, L.c_p, L.c_i, ctypes.c_longlong] + [L.c_f] * 6 + [L.c_i] * 4 + [L.c_p] * 3 + [ctypes.c_longlong, L.c_p,
                                L.c_p, L.c_sz, L.c_p]),
+    "mcav_pillarize_indexed": (L.c_i, [L.c_p, L.c_p, L.c_i, ctypes.c_longlong] + [L.c_f] * 6 + [L.c_i] * 4 + [L.c_p] * 3 +
+                               [ctypes.c_longlong, L.c_p, L.c_p, L.c_p, L.c_sz, L.c_p]),
+    "mcav_pillarize_bwd": (L.c_i, [L.c_p] * 4 + [L.c_i, ctypes.c_longlong, L.c_i, L.c_i, L.c_p, ctypes.c_longlong, L.c_p]),
     "mcav_gdc_workspace_bytes": (L.c_sz, [L.c_i] * 5),
     "mcav_gdc_graph": (L.c_i, [L.c_p] * 3 + [L.c_i] * 5 + [L.c_f] * 3 + [L.c_p] * 4 + [L.c_sz, L.c_p]),
     "mcav_gdc_solve": (L.c_i, [L.c_p] * 5 + [L.c_i] * 7 + [L.c_f] + [L.c_p] * 3 + [L.c_sz, L.c_p]),
@@ -102,6 +117,9 @@ class CloudBatch:
         self._host = None
         self._meta_bytes, self._meta, self._ws = None, None, None       # project_batch's calibration table and workspace
         self.ground, self._packed, self._scales = None, None, None      # scale="ground": the estimate, its scales packed; the [B] scales in use
+        self.pixels = None                                              # int32 [capacity] with provenance: the pixel behind every row
+        self._fwd, self._bwd_ws, self._stamp = None, [None], 0          # what project_batch_backward reads, its workspace (boxed: the
+                                                                        # graph nodes of this object share it); calls so far
 
     def __len__(self):
         return self.offsets.numel() - 1
@@ -130,7 +148,7 @@ class CloudBatch:
             host[int(o[b]):int(o[b + 1])].tofile(path)
 
     def pillars(self, **kw):
-        """pillarize(self.points, self.offsets, **kw) -> PillarBatch (grid, max_points, capacity, decorate, out)"""
+        """pillarize(self.points, self.offsets, **kw) -> PillarBatch (grid, max_points, capacity, decorate, out, provenance)"""
         return pillarize(self.points, self.offsets, **kw)
 
 
@@ -180,6 +198,8 @@ class PillarBatch:
         self.offsets = torch.zeros(int(batch) + 1, dtype=torch.int32, device=device)
         self.grid = None
         self._host, self._ws = None, None
+        self.slot_points = None                                         # int32 [capacity, N] with provenance: the cloud row in every slot
+        self._fwd, self._stamp = None, 0                                # what pillarize_backward reads; calls so far
 
     def __len__(self):
         return self.offsets.numel() - 1
@@ -230,13 +250,18 @@ class PillarBatch:
                 np.savez(f, **arrays)
 
 
-def pillarize(points, offsets, grid=None, max_points=32, capacity=None, decorate=False, out=None):
+def pillarize(points, offsets, grid=None, max_points=32, capacity=None, decorate=False, out=None, provenance=False):
     """A cloud batch -> pillars (mcav_pillarize).  points: [n_max, 4] float32 (x, y, z, i) and offsets: int32 [B + 1] on the GPU, as a
     CloudBatch holds them (rows at and beyond offsets[B] are never read).  grid: a PillarGrid (default: PointPillars' KITTI grid).
     max_points: N, the slots of a pillar, 1..64: the first N points of the cell in cloud order.  capacity: the rows of the output, default
     min(n_max, B * ny * nx) -- every pillar there can be; with fewer, the pillars beyond are dropped and offsets stay exact.
     decorate: C = 9 instead of 4: PointPillars' offsets from the pillar's mean (3) and from the cell's centre (2).
-    out: a PillarBatch to reuse with its workspace (needed under graph capture).  -> PillarBatch; no host synchronisation."""
+    out: a PillarBatch to reuse with its workspace (needed under graph capture).  -> PillarBatch; no host synchronisation.
+    provenance: also fill out.slot_points, int32 [capacity, N]: the row of `points` every slot holds, -1 in the zero-padded slots
+    (mcav_pillarize_indexed; everything else is the same, bit for bit); pillarize_backward then works on the result.
+    Differentiable: with grad mode on and points that require a gradient (a differentiable project_batch's) the call is a node of the
+    autograd graph -- out.voxels carries the grad_fn, out.slot_points is filled -- whose backward is pillarize_backward
+    (mcav_pillarize_bwd).  The PillarBatch must not be filled again before backward runs."""
     if not torch.is_tensor(points) or not torch.is_tensor(offsets):
         raise L.MCAVError("pillarize: points and offsets must be tensors on the GPU")
     if points.dim() != 2 or points.shape[1] != 4:
@@ -278,10 +303,33 @@ def pillarize(points, offsets, grid=None, max_points=32, capacity=None, decorate
     out._host, out.grid = None, grid
     if out._ws is None or out._ws.numel() < nbytes:
         out._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        L.check(hl.mcav_pillarize(L.ptr(points), L.ptr(offsets), B, n_max, *grid.scalars(), grid.nx, grid.ny, N,
-                                  PILLAR_DECORATE if decorate else 0, L.ptr(out.voxels), L.ptr(out.coords), L.ptr(out.num_points), capacity,
-                                  L.ptr(out.offsets), L.ptr(out._ws), out._ws.numel(), L.stream()), "mcav_pillarize")
+    wants_grad = torch.is_grad_enabled() and points.requires_grad
+    indexed = wants_grad or bool(provenance)
+    if out.voxels.grad_fn is not None:
+        out.voxels = out.voxels.detach()                     # an earlier differentiable call's node: the buffer itself
+    if indexed and (out.slot_points is None or tuple(out.slot_points.shape) != (capacity, N)):
+        out.slot_points = torch.empty((capacity, N), dtype=torch.int32, device=dev)
+    elif not indexed:
+        out.slot_points = None                               # nothing filled them in this call
+    # what the backward reads: the selection and the counts this call leaves, not the object (a graph node must not keep it alive)
+    out._fwd = dict(slot_points=out.slot_points, num_points=out.num_points, offsets=out.offsets, n_max=n_max, B=B,
+                    shape=(capacity, N, C)) if indexed else None
+
+    def run():
+        with torch.cuda.device(dev):
+            head = (L.ptr(points), L.ptr(offsets), B, n_max, *grid.scalars(), grid.nx, grid.ny, N, PILLAR_DECORATE if decorate else 0,
+                    L.ptr(out.voxels), L.ptr(out.coords), L.ptr(out.num_points), capacity, L.ptr(out.offsets))
+            tail = (L.ptr(out._ws), out._ws.numel(), L.stream())
+            if indexed:
+                L.check(hl.mcav_pillarize_indexed(*head, L.ptr(out.slot_points), *tail), "mcav_pillarize_indexed")
+            else:
+                L.check(hl.mcav_pillarize(*head, *tail), "mcav_pillarize")
+
+    out._stamp += 1
+    if wants_grad:
+        out.voxels = _PillarizeFunction.apply(points, out, run)
+    else:
+        run()
     return out
 
 
@@ -516,7 +564,7 @@ class PseudoLiDAR:
         return ground_scale(m, sizes=sizes, P=self.P if P is None else P, **kw)
 
     def project_batch(self, m, sizes=None, P=None, T=None, input="disparity", scale=1.0, intensity=None, max_height=1.0, max_depth=None,
-                      beams=None, out=None, padded=None, ground=None):
+                      beams=None, out=None, padded=None, ground=None, provenance=False):
         """m: [B, h, w] or [B, 1, h, w] float32 on the GPU -- the network's sigmoid disparity, or depths with input="depth".
         sizes: B pairs (Hb, Wb), the resolution P describes (default: (h, w)); padded: (Hg, Wg) bounding them (default: the largest).
         P [3, 4] / [B, 3, 4], T [4, 4] / [B, 4, 4]: default the instance's.  scale multiplies the depth (pred_depth_scale_factor): a
@@ -527,7 +575,14 @@ class PseudoLiDAR:
         every call: under graph capture hand over a contiguous one.
         intensity: a plane shaped as m for the 4th column (default 0).  max_height: the reference's max_high cut; max_depth: None = off.
         beams: a beam_tables result = one return per cell instead of the dense cloud; self.sparsity applies to the dense cloud only.
-        out: a CloudBatch to reuse (needed under graph capture).  -> CloudBatch; no host synchronisation."""
+        out: a CloudBatch to reuse (needed under graph capture).  -> CloudBatch; no host synchronisation.
+        provenance: also fill out.pixels, int32 [capacity]: the pixel r * Wg + c of its image's padded grid that became each row
+        (mcav_pl_batch_project_indexed; the cloud is the same, bit for bit); project_batch_backward then works on the result.
+        Differentiable: with grad mode on and an m that requires a gradient the call is a node of the autograd graph -- out.points carries
+        the grad_fn, out.pixels is filled -- whose backward is project_batch_backward (mcav_pl_batch_project_bwd) on the current stream.
+        Only m gets a gradient: which pixels survive the cuts, the sparsifier and the beam grid is piecewise constant, and scale, a scale
+        tensor, scale="ground" (the estimate is a median, taken as a constant), intensity and the calibration are constants.  The
+        CloudBatch must not be projected into again, nor the plane changed in place, before backward runs (both are refused)."""
         m = _plane(m, "project_batch")
         B, h, w = m.shape
         if input not in ("disparity", "depth"):
@@ -598,15 +653,155 @@ class PseudoLiDAR:
             scales, scale = L.dev(scale.contiguous() if scale.is_cuda else scale, "scale"), 1.0
         elif ground is not None:
             raise L.MCAVError("project_batch: ground= has no meaning without scale='ground'")
-        with torch.cuda.device(dev):
-            head = (L.ptr(m), B, h, w, Hg, Wg, L.c_p(meta.data_ptr() + 224 * B), L.c_p(meta.data_ptr()), L.ptr(intensity), L.ptr(elev),
-                    L.ptr(azim), nb, na, float(scale))
-            tail = (float(max_height), float("inf") if max_depth is None else float(max_depth), sparsity,
-                    PLB_INPUT_DEPTH if input == "depth" else 0, L.ptr(out.points), out.points.shape[0], L.ptr(out.offsets), L.ptr(ws),
-                    ws.numel(), L.stream())
-            if scales is None:
-                L.check(hl.mcav_pl_batch_project(*head, *tail), "mcav_pl_batch_project")
-            else:
-                out._scales = scales                                                   # alive as long as the cloud is
-                L.check(hl.mcav_pl_batch_project_scaled(*head, L.ptr(scales), *tail), "mcav_pl_batch_project_scaled")
+        flags = PLB_INPUT_DEPTH if input == "depth" else 0
+        wants_grad = torch.is_grad_enabled() and m.requires_grad
+        indexed = wants_grad or bool(provenance)
+        if out.points.grad_fn is not None:
+            out.points = out.points.detach()                                           # an earlier differentiable call's node: the buffer itself
+        if indexed and (out.pixels is None or out.pixels.shape[0] != out.points.shape[0]):
+            out.pixels = torch.empty(out.points.shape[0], dtype=torch.int32, device=dev)
+        elif not indexed:
+            out.pixels = None                                                          # nothing filled them in this call
+        if scales is not None:
+            out._scales = scales                                                       # alive as long as the cloud is
+
+        def run():
+            with torch.cuda.device(dev):
+                head = (L.ptr(m), B, h, w, Hg, Wg, L.c_p(meta.data_ptr() + 224 * B), L.c_p(meta.data_ptr()), L.ptr(intensity), L.ptr(elev),
+                        L.ptr(azim), nb, na, float(scale))
+                mid = (float(max_height), float("inf") if max_depth is None else float(max_depth), sparsity, flags, L.ptr(out.points),
+                       out.points.shape[0], L.ptr(out.offsets))
+                tail = (L.ptr(ws), ws.numel(), L.stream())
+                if indexed:
+                    L.check(hl.mcav_pl_batch_project_indexed(*head, L.ptr(scales), *mid, L.ptr(out.pixels), *tail), "mcav_pl_batch_project_indexed")
+                elif scales is None:
+                    L.check(hl.mcav_pl_batch_project(*head, *mid, *tail), "mcav_pl_batch_project")
+                else:
+                    L.check(hl.mcav_pl_batch_project_scaled(*head, L.ptr(scales), *mid, *tail), "mcav_pl_batch_project_scaled")
+
+        out._stamp += 1
+        # what the backward reads besides the cloud: the plane, the table this call used, the scale as the kernels took it
+        # (not the object: a graph node must not keep it alive)
+        out._fwd = dict(m=m.detach(), meta=meta, scale=float(scale), scales=scales, flags=flags, padded=(Hg, Wg), pixels=out.pixels,
+                        offsets=out.offsets, capacity=out.points.shape[0], ws=out._bwd_ws) if indexed else None
+        if wants_grad:
+            out.points = _ProjectFunction.apply(m, out, run)
+        else:
+            run()
         return out
+
+
+def project_batch_backward(cloud, grad_points, out=None):
+    """The backward of project_batch as a plain call (mcav_pl_batch_project_bwd; a memset and two launches, no host synchronisation).
+    cloud: a CloudBatch filled by project_batch with provenance=True (or by a differentiable call), its points, offsets, pixels and the
+    plane it was made from still holding what they held; grad_points: [capacity, 4] float32, the gradient of cloud.points (column 3 is
+    ignored, rows behind the count are never read).  -> d_m [B, h, w] float32, every element written: the float64 sum over the resized
+    pixels whose taps touch it, no atomics, the same bytes from run to run.  out: a tensor to fill (else a new one; under graph capture it
+    comes from the capture's pool).  The workspace lives on the CloudBatch."""
+    if not isinstance(cloud, CloudBatch):
+        raise L.MCAVError("project_batch_backward: cloud must be a CloudBatch, got %r" % type(cloud).__name__)
+    if cloud._fwd is None or cloud.pixels is None:
+        raise L.MCAVError("project_batch_backward: the CloudBatch holds no provenance (project_batch(..., provenance=True) records it)")
+    return _project_backward(cloud._fwd, grad_points, out)
+
+
+def _project_backward(f, grad_points, out):
+    m, (Hg, Wg), cap, box = f["m"], f["padded"], f["capacity"], f["ws"]
+    B, h, w = m.shape
+    if not torch.is_tensor(grad_points) or tuple(grad_points.shape) != (cap, 4):
+        raise L.MCAVError("project_batch_backward: grad_points must be [%d, 4]" % cap)
+    dev = m.device
+    if L.dev(grad_points, "grad_points").device != dev:
+        raise L.MCAVError("project_batch_backward: grad_points is on %s, the cloud on %s" % (grad_points.device, dev))
+    if out is None:
+        out = torch.empty((B, h, w), dtype=torch.float32, device=dev)
+    elif not torch.is_tensor(out) or tuple(out.shape) != (B, h, w) or L.dev(out, "out").device != dev:
+        raise L.MCAVError("project_batch_backward: out must be float32 %s on %s" % ([B, h, w], dev))
+    hl = L.lib()
+    nbytes = hl.mcav_pl_batch_project_bwd_workspace_bytes(B, Hg, Wg)
+    if nbytes == 0:
+        raise L.MCAVError("project_batch_backward: a batch of %d x %d x %d pixels is refused" % (B, Hg, Wg))
+    if box[0] is None or box[0].numel() < nbytes:
+        box[0] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    ws, meta = box[0], f["meta"]
+    with torch.cuda.device(dev):
+        L.check(hl.mcav_pl_batch_project_bwd(L.ptr(grad_points), cap, L.ptr(f["pixels"]), L.ptr(f["offsets"]), L.ptr(m), B, h, w, Hg, Wg,
+                                             L.c_p(meta.data_ptr() + 224 * B), L.c_p(meta.data_ptr()), f["scale"], L.ptr(f["scales"]), f["flags"],
+                                             L.ptr(out), L.ptr(ws), ws.numel(), L.stream()), "mcav_pl_batch_project_bwd")
+    return out
+
+
+class _ProjectFunction(torch.autograd.Function):
+    """project_batch as one node of the autograd graph: the forward is the indexed call into the CloudBatch's buffer (returned as a new
+    tensor on the same memory), the backward mcav_pl_batch_project_bwd on what that call recorded.  The node holds the tensors, not the
+    CloudBatch (the CloudBatch holds the node through `points`); the plane, the pixels and the offsets go through save_for_backward, so an
+    in-place torch operation on any of them before backward is refused by autograd, and a second projection into the same CloudBatch
+    (whose kernels write them behind autograd's back) by the stamp."""
+
+    @staticmethod
+    def forward(ctx, m, cloud, run):
+        ctx.fwd, ctx.stamp, ctx.owner = cloud._fwd, cloud._stamp, weakref.ref(cloud)
+        run()
+        ctx.save_for_backward(m, cloud.pixels, cloud.offsets)
+        return cloud.points.detach()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        ctx.saved_tensors                                    # the version check
+        cloud = ctx.owner()
+        if cloud is not None and cloud._stamp != ctx.stamp:
+            raise L.MCAVError("backward: the CloudBatch was projected into again after this forward")
+        return _project_backward(ctx.fwd, grad.to(torch.float32).contiguous(), None), None, None
+
+
+def pillarize_backward(pillars, grad_voxels, out=None):
+    """The backward of pillarize as a plain call (mcav_pillarize_bwd; a memset and one launch, no host synchronisation).  pillars: a
+    PillarBatch filled by pillarize with provenance=True (or by a differentiable call), its num_points, offsets and slot_points still
+    holding what they held; grad_voxels: [capacity, N, C] float32 (rows behind the pillar count are never read).  -> d_points [n_max, 4]
+    float32, every row written: a row that no slot holds gets +0.0.  With decorated columns the offsets from the pillar's mean pass their
+    gradient on to every point of the pillar; which point lands in which slot is piecewise constant and has no gradient.  out: a tensor
+    to fill (else a new one)."""
+    if not isinstance(pillars, PillarBatch):
+        raise L.MCAVError("pillarize_backward: pillars must be a PillarBatch, got %r" % type(pillars).__name__)
+    if pillars._fwd is None or pillars.slot_points is None:
+        raise L.MCAVError("pillarize_backward: the PillarBatch holds no provenance (pillarize(..., provenance=True) records it)")
+    return _pillarize_backward(pillars._fwd, grad_voxels, out)
+
+
+def _pillarize_backward(f, grad_voxels, out):
+    (cap, N, C), n_max, B, dev = f["shape"], f["n_max"], f["B"], f["slot_points"].device
+    if not torch.is_tensor(grad_voxels) or tuple(grad_voxels.shape) != (cap, N, C):
+        raise L.MCAVError("pillarize_backward: grad_voxels must be [%d, %d, %d]" % (cap, N, C))
+    if L.dev(grad_voxels, "grad_voxels").device != dev:
+        raise L.MCAVError("pillarize_backward: grad_voxels is on %s, the pillars on %s" % (grad_voxels.device, dev))
+    if out is None:
+        out = torch.empty((n_max, 4), dtype=torch.float32, device=dev)
+    elif not torch.is_tensor(out) or tuple(out.shape) != (n_max, 4) or L.dev(out, "out").device != dev:
+        raise L.MCAVError("pillarize_backward: out must be float32 %s on %s" % ([n_max, 4], dev))
+    with torch.cuda.device(dev):
+        L.check(L.lib().mcav_pillarize_bwd(L.ptr(grad_voxels), L.ptr(f["slot_points"]), L.ptr(f["num_points"]), L.ptr(f["offsets"]), B, cap, N,
+                                           PILLAR_DECORATE if C == 9 else 0, L.ptr(out), n_max, L.stream()), "mcav_pillarize_bwd")
+    return out
+
+
+class _PillarizeFunction(torch.autograd.Function):
+    """pillarize as one node of the autograd graph: the forward is the indexed call into the PillarBatch's buffers (the voxels returned as
+    a new tensor on the same memory), the backward mcav_pillarize_bwd on what that call recorded; as _ProjectFunction, the node holds the
+    tensors (slot_points, num_points and offsets through save_for_backward), not the PillarBatch."""
+
+    @staticmethod
+    def forward(ctx, points, pillars, run):
+        ctx.fwd, ctx.stamp, ctx.owner = pillars._fwd, pillars._stamp, weakref.ref(pillars)
+        run()
+        ctx.save_for_backward(pillars.slot_points, pillars.num_points, pillars.offsets)
+        return pillars.voxels.detach()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        ctx.saved_tensors                                    # the version check
+        pillars = ctx.owner()
+        if pillars is not None and pillars._stamp != ctx.stamp:
+            raise L.MCAVError("backward: the PillarBatch was filled again after this forward")
+        return _pillarize_backward(ctx.fwd, grad.to(torch.float32).contiguous(), None), None, None
