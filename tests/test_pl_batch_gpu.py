@@ -269,3 +269,45 @@ def test_inference_exports_a_drive(tmp_path, monkeypatch):
         bits_equal(beams.points[:int(bwoff[-1])], bwant)
     assert seen == 4
     t.set_train()
+
+
+def test_calibration_upload_and_workspace_are_kept():
+    """project_batch, ground_scale and gdc with out=: equal calibration leaves the device table and the workspace where they are (nothing
+    is copied or allocated: what a capture's warm-up relies on); one changed matrix entry replaces the table, the workspace stays, and the
+    result is a fresh object's, bit for bit (and not the first call's)."""
+    import gdc_cases as DC
+    import ground_scale_cases as GC
+    from pseudo_lidar import gdc, ground_scale
+    a, g, d = C.build("direct-dense"), GC.build("flat"), DC.build("full")          # the smallest case of each module's list
+    gm, depth, sparse = torch.tensor(g["m"], device=DEV), torch.tensor(d["depth"], device=DEV), torch.tensor(d["sparse"], device=DEV)
+    gkw = dict(sizes=g["sizes"], camera_height=g["camera_height"], max_angle_deg=g["max_angle_deg"], box=g["boxes"],
+               min_ground=g["min_ground"], fallback=g["fallback"], input=g["input"], keep_mask=True)
+
+    def cloud(P, out):
+        cb = run(dict(a, P=P), out=out)
+        return cb, (cb.offsets, cb.points[:int(cb.counts()[-1])].view(torch.int32))
+
+    def scale(P, out):
+        gs = ground_scale(gm, P=P, out=out, **gkw)
+        return gs, (gs.rows.view(torch.int32), gs.mask)
+
+    def corrected(K, out):
+        res = gdc(depth, sparse, K, min_known=d["min_known"], out=out, **d["params"])
+        return res, (res.depth.view(torch.int32), res.info.view(torch.int32), res.nbr, res.weights.view(torch.int32))
+
+    for stage, calib, entry in ((cloud, a["P"], (0, 0, 2)), (scale, g["P"], (0, 0, 0)), (corrected, d["K"], (0, 0))):
+        changed = np.array(calib)
+        changed[entry] *= 1.5
+        out, first = stage(calib, None)
+        first = [t.clone() for t in first]
+        table, ws = out._uploaded, out._ws
+        at = table.data_ptr(), ws.data_ptr()
+        again, second = stage(np.array(calib), out)                                # equal values in another array
+        assert again is out and out._uploaded is table and out._ws is ws and (table.data_ptr(), ws.data_ptr()) == at
+        assert all(torch.equal(x, y) for x, y in zip(first, second))
+        _, third = stage(changed, out)
+        assert out._uploaded is not table and out._uploaded.data_ptr() != at[0]          # (the old one is still alive here)
+        assert out._ws is ws and ws.data_ptr() == at[1]
+        fresh = stage(changed, None)[1]
+        assert all(x.shape == y.shape and torch.equal(x, y) for x, y in zip(third, fresh)), stage.__name__
+        assert not all(x.shape == y.shape and torch.equal(x, y) for x, y in zip(third, first)), stage.__name__

@@ -18,7 +18,7 @@ import torch
 
 from mcav import lib as L
 
-from .PseudoLiDAR import PillarBatch, PillarGrid
+from .clouds import PillarBatch, PillarGrid
 
 L.register({
     "mcav_pillar_pseudo_image": (L.c_i, [L.c_p] * 4 + [L.c_i, ctypes.c_longlong] + [L.c_i] * 4 + [L.c_p] * 3 + [L.c_i, L.c_i] + [L.c_p] * 3),
