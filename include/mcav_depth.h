@@ -563,6 +563,39 @@ int mcav_pillar_pseudo_image_bwd(const float* voxels, const int* coords, const i
                                  float* d_weight, float* d_bias, float* d_bias_pad, float* d_voxels /* may be null */,
                                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* The moments of a PillarBatch's used voxel slots: what training-mode BatchNorm statistics behind a linear layer without bias follow from.
+ * With y = W x over all P max_points rows of the padded [P, max_points, columns] tensor (a zero-padded slot gives y = 0, as
+ * second.pytorch's masked rows do), mean_o = w_o . s / rows and E[y_o^2] = w_o^T M w_o / rows.  The definition is tests/pfn_stats_ref.py;
+ * the arithmetic is csrc/pfn_stats_math.h.  voxels, num_points, pillar_offsets, B, capacity, max_points, columns: as
+ * mcav_pillar_pseudo_image takes them, with the same P = min(pillar_offsets[B], capacity) and n = num_points[p] clamped to
+ * [0, max_points]; unused slots and rows at and beyond P are never read.
+ *   moments  device float64 [2 + columns + columns^2]:
+ *            [0]  rows = P max_points;  [1]  used = the sum of n over p < P
+ *            [2 .. 2 + columns)  s[c] = the sum of voxels[p, k, c] over the used slots (p < P, k < n)
+ *            the rest  M[c][c'] = the sum of voxels[p, k, c] voxels[p, k, c'], row-major, both halves holding the same bits
+ *            A term is the float64 product of two float32 values (exact); the sums are float64 in a fixed order.  Non-finite used
+ *            values propagate.
+ * No atomics, two runs give the same bytes; no host synchronisation, allocation or copy: the call can be captured.  2 launches.
+ * Workspace: mcav_pillar_moments_workspace_bytes (0 for sizes that are refused): 8 (1 + columns + columns (columns + 1) / 2)
+ * min(ceil(capacity / 256), 512) bytes rounded up to 256, scratch of one call, no zero-fill.
+ * Returns MCAV_E_INVALID for a null voxels, num_points, pillar_offsets, moments or workspace, an address that is no multiple of 4 (moments
+ * and the workspace: of 8), B <= 0, B > 65535, capacity < 0, max_points outside [1, 64] or columns outside {4, 9}; MCAV_E_WORKSPACE for a
+ * short workspace; nothing is launched then. */
+size_t mcav_pillar_moments_workspace_bytes(long long capacity, int max_points, int columns);
+int mcav_pillar_moments(const float* voxels, const int* num_points, const int* pillar_offsets, int B, long long capacity,
+                        int max_points, int columns, double* moments, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The adjoint of mcav_pillar_moments: from g [columns] float64, the gradient with respect to s, and H [columns, columns] float64, the
+ * gradient with respect to M (any matrix), to the gradient of the voxels.  rows and used have no gradient.
+ *   d_voxels device [capacity, max_points, columns] float32, every element written: for a used slot acc = g[c], then for c' ascending
+ *            acc = fma(H[c][c'] + H[c'][c], (double)voxels[p, k, c'], acc) in float64, stored as (float)acc: one rounding; +0.0 in unused
+ *            slots and in rows at and beyond P.
+ * Two runs give the same bytes; no host synchronisation, allocation or copy: the call can be captured.  1 launch.
+ * Returns MCAV_E_INVALID for what mcav_pillar_moments refuses of the shared arguments, a null g, H or d_voxels, or a g or H whose address
+ * is no multiple of 8; nothing is launched then. */
+int mcav_pillar_moments_bwd(const float* voxels, const int* num_points, const int* pillar_offsets, int B, long long capacity,
+                            int max_points, int columns, const double* g, const double* H, float* d_voxels, void* stream);
+
 /* Graph-based depth correction from sparse LiDAR (GDC): You et al., "Pseudo-LiDAR++: Accurate Depth for 3D Object Detection in Autonomous
  * Driving", ICLR 2020, section 4; the reference's notes pseudo-lidar/PL_development/research/pseudo_lidar++.md: "create a KNN graph; use
  * sparse LiDAR point clouds to bias and correct depth".  A predicted depth map has the right local shape and a smooth error; a few exact

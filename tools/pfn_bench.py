@@ -3,7 +3,7 @@
 192 x 640 disparities (a seeded scene: tests/pl_batch_cases.py) at 375 x 1242, dense and as 64 x 512 beams (as tools/pillar_bench.py builds
 them), voxelised on PointPillars' KITTI grid (432 x 496) with N = 32 slots and the 9 decorated columns, under a seeded layer of 64 channels:
 the canvas is 12 x 64 x 496 x 432 float32 = 658 MB.
-usage: python tools/pfn_bench.py [--batch 12] [--iters 30] [--rounds 3] [--points 32] [--channels 64] [--backward]
+usage: python tools/pfn_bench.py [--batch 12] [--iters 30] [--rounds 3] [--points 32] [--channels 64] [--backward | --batch-stats]
   nchw / nhwc  PillarFeatureNet.pseudo_image(out=...) (mcav_pillar_pseudo_image: one launch), nothing read back
   features     PillarFeatureNet.features(out=...): the layer alone, no canvas
   torch        the stock formulation on the same device and inputs: F.linear over [P, N, C], the folded BatchNorm as a scale and a shift,
@@ -19,7 +19,15 @@ share of 8 TB/s they make at the nchw median; the canvas alone is the floor: a m
   torch_fwdbwd[_vox]     autograd through the stock formulation above, forward and backward, the parameters (and the voxels) requiring a
                          gradient; torch_fwd is its forward with the graph recorded
 bytes: what a backward must move -- read: P N C 4 + 24 P + P C_out 4 of the gradient (an NCHW gradient comes in 32-byte sectors, so up to
-8 times that); written: capacity N C 4 for d_voxels and the slab -- and their share of 8 TB/s at the median."""
+8 times that); written: capacity N C 4 for d_voxels and the slab -- and their share of 8 TB/s at the median.
+--batch-stats times training-mode BatchNorm statistics from the voxels' moments on the same clouds:
+  moments / moments_bwd  pillar_moments(out=...) (mcav_pillar_moments: two launches) and pillar_moments_backward(out=...) (one launch)
+  voxels_sum             torch.sum over the whole voxels tensor: the floor of a pass over it, as the memset is the canvas's
+  step_batch             PillarFeatureLayer(batch_stats=True) in train(): forward to the NCHW canvas, backward under a seeded normal canvas
+                         gradient with the voxels requiring a gradient, the buffers' update
+  step_frozen            the same step of the default layer (frozen statistics): the difference is what batch statistics cost
+  torch_step             autograd through F.linear -> BatchNorm1d(train) over the [P N, C_out] rows -> relu -> max -> indexed scatter, the
+                         voxels requiring a gradient"""
 import argparse
 import json
 import os
@@ -31,7 +39,8 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import pl_batch_cases as PC  # noqa: E402
-from pseudo_lidar import PillarFeatureNet, PillarGrid, PseudoLiDAR, beam_tables  # noqa: E402
+from pseudo_lidar import (PillarFeatureLayer, PillarFeatureNet, PillarGrid, PseudoLiDAR, beam_tables, pillar_moments,  # noqa: E402
+                          pillar_moments_backward)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=12)
@@ -40,6 +49,7 @@ ap.add_argument("--rounds", type=int, default=3)
 ap.add_argument("--points", type=int, default=32)
 ap.add_argument("--channels", type=int, default=64)
 ap.add_argument("--backward", action="store_true")
+ap.add_argument("--batch-stats", action="store_true")
 a = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("pfn_bench: needs the GPU; a CPU run says nothing about these times")
@@ -136,10 +146,72 @@ def backward_runs(kind, pb):
     return entry
 
 
+def batch_stats_runs(kind, pb):
+    """-> the --batch-stats entry of one cloud kind"""
+    P, cap = int(min(pb.counts()[-1], pb.voxels.shape[0])), pb.voxels.shape[0]
+    idx = pb.coords[:P].long()
+    ib, iy, ix = idx[:, 0].contiguous(), idx[:, 2].contiguous(), idx[:, 3].contiguous()
+    up = torch.randn(shape, device=dev, generator=torch.Generator(device=dev).manual_seed(9))
+    layers = {}
+    for key, flag in (("step_batch", True), ("step_frozen", False)):
+        layer = PillarFeatureLayer(9, CO, batch_stats=flag).to(dev).train()
+        with torch.no_grad():
+            layer.linear.weight.copy_(weight)
+            layer.norm.weight.copy_(scale)
+            layer.norm.bias.copy_(shift)
+        layers[key] = layer
+    moments = torch.empty(92, dtype=torch.float64, device=dev)
+    grad = torch.randn(92, dtype=torch.float64, device=dev, generator=torch.Generator(device=dev).manual_seed(10))
+    d_vox = torch.empty_like(pb.voxels)
+    stock = torch.nn.BatchNorm1d(CO, eps=1e-3).to(dev).train()
+    wt = weight.clone().requires_grad_(True)
+
+    def step(layer):
+        for p in layer.parameters():
+            p.grad = None
+        pb.voxels.grad = None
+        layer(pb).backward(up)
+
+    def torch_step():
+        v = pb.voxels[:P].detach().requires_grad_(True)
+        wt.grad = stock.weight.grad = stock.bias.grad = None
+        y = stock(torch.nn.functional.linear(v, wt).reshape(P * N, CO)).reshape(P, N, CO)
+        c = torch.zeros(shape, device=dev)
+        c[ib, :, iy, ix] = torch.relu(y).max(dim=1).values
+        c.backward(up)
+
+    runs = {"moments": lambda: pillar_moments(pb, out=moments), "moments_bwd": lambda: pillar_moments_backward(pb, grad, out=d_vox),
+            "voxels_sum": lambda: torch.sum(pb.voxels)}
+    pb.voxels.requires_grad_(True)
+    runs.update({k: (lambda layer=layer: step(layer)) for k, layer in layers.items()})
+    runs["torch_step"] = torch_step
+    plain = ("moments", "moments_bwd", "voxels_sum")
+    rounds = {k: [] for k in runs}
+    for k, fn in runs.items():
+        with torch.set_grad_enabled(k not in plain):
+            for _ in range(5):
+                fn()
+    for _ in range(a.rounds):
+        for k, fn in runs.items():
+            with torch.set_grad_enabled(k not in plain):
+                rounds[k].append(round(kernels(fn), 1))
+    pb.voxels.requires_grad_(False)
+    pb.voxels.grad = None
+    used = int(pillar_moments(pb)[1])
+    us = {k: med(v) for k, v in rounds.items()}
+    return {"pillars": P, "capacity": cap, "used_slots": used, "points_per_pillar": round(used / max(P, 1), 2),
+            "us_per_dispatch": {k: {"rounds": v, "median": med(v)} for k, v in rounds.items()},
+            "batch_statistics_cost_us": round(us["step_batch"] - us["step_frozen"], 1),
+            "torch_step_over_step_batch": round(us["torch_step"] / us["step_batch"], 2),
+            "moments_bytes_read": used * 36 + 4 * P, "moments_gbytes_per_s": round((used * 36 + 4 * P) / us["moments"] / 1e3, 1),
+            "moments_bwd_bytes_written": cap * N * 36, "moments_bwd_gbytes_per_s": round(cap * N * 36 / us["moments_bwd"] / 1e3, 1),
+            "torch_intermediate_bytes": 4 * P * N * CO}
+
+
 for kind, cb in clouds.items():
     pb = cb.pillars(grid=grid, max_points=N, decorate=True)
-    if a.backward:
-        result["runs"][kind] = backward_runs(kind, pb)
+    if a.backward or a.batch_stats:
+        result["runs"][kind] = (backward_runs if a.backward else batch_stats_runs)(kind, pb)
         continue
     P = int(min(pb.counts()[-1], pb.voxels.shape[0]))
     feat = torch.empty((pb.voxels.shape[0], CO), device=dev)

@@ -9,7 +9,9 @@ Nothing is read back.
 Both calls are differentiable: when grad mode is on and the weight, the bias, bias_pad or the pillars' voxels require a gradient they run
 through one torch.autograd.Function whose backward is `gradients` (mcav_pillar_pseudo_image_bwd; the definition is tests/pfn_bwd_ref.py),
 which recomputes the layer and keeps nothing of the forward.  `PillarFeatureLayer` is the torch.nn.Module with a PFNLayer's state dict
-that fine-tunes the layer on pseudo-LiDAR clouds.
+that fine-tunes the layer on pseudo-LiDAR clouds, and with batch_stats=True trains it with BatchNorm's batch statistics: `pillar_moments`
+(mcav_pillar_moments; the definition is tests/pfn_stats_ref.py) sums the used voxel slots and their products once, `fold_batch` turns the
+moments into the folded layer, and `pillar_moments_backward` (mcav_pillar_moments_bwd) carries the statistics' gradient to the voxels.
 """
 import ctypes
 
@@ -25,6 +27,9 @@ L.register({
     "mcav_pillar_pseudo_image_bwd_workspace_bytes": (L.c_sz, [ctypes.c_longlong, L.c_i, L.c_i]),
     "mcav_pillar_pseudo_image_bwd": (L.c_i, [L.c_p] * 4 + [L.c_i, ctypes.c_longlong] + [L.c_i] * 4 + [L.c_p] * 3 + [L.c_i, L.c_i] + [L.c_p] * 6 +
                                      [L.c_p, L.c_sz, L.c_p]),
+    "mcav_pillar_moments_workspace_bytes": (L.c_sz, [ctypes.c_longlong, L.c_i, L.c_i]),
+    "mcav_pillar_moments": (L.c_i, [L.c_p] * 3 + [L.c_i, ctypes.c_longlong, L.c_i, L.c_i] + [L.c_p] * 2 + [L.c_sz, L.c_p]),
+    "mcav_pillar_moments_bwd": (L.c_i, [L.c_p] * 3 + [L.c_i, ctypes.c_longlong, L.c_i, L.c_i] + [L.c_p] * 4),
 })
 
 PFN_NHWC = 1                                   # include/mcav_depth.h MCAV_PFN_NHWC
@@ -42,6 +47,164 @@ def _f64(sd, key, shape=None, optional=False):
     if shape is not None and v.shape != shape:
         raise L.MCAVError("PillarFeatureNet: %r is %s, expected %s" % (key, list(v.shape), list(shape)))
     return v
+
+
+def _checked_pillars(pillars, what, columns=None, device=None, need_grid=False):
+    """-> capacity, B.  Shapes, columns and the grid first, devices and dtypes last: what can be refused without a GPU is.  columns: what a
+    layer takes (None: 4 or 9); device: the layer's (None: the voxels')"""
+    if not isinstance(pillars, PillarBatch):
+        raise L.MCAVError("%s: pillars must be a PillarBatch, got %r" % (what, type(pillars).__name__))
+    vox = pillars.voxels
+    if not torch.is_tensor(vox) or vox.dim() != 3 or not 1 <= vox.shape[1] <= 64:
+        raise L.MCAVError("%s: voxels must be [capacity, N <= 64, C]" % what)
+    if columns is None and vox.shape[2] not in COLUMNS:
+        raise L.MCAVError("%s: the pillars have %d columns, not 4 or 9" % (what, vox.shape[2]))
+    if columns is not None and vox.shape[2] != columns:
+        raise L.MCAVError("%s: the pillars have %d columns, the layer takes %d" % (what, vox.shape[2], columns))
+    cap, B = vox.shape[0], len(pillars)
+    if B < 1 or cap < 1:
+        raise L.MCAVError("%s: an empty PillarBatch" % what)
+    buffers = ((pillars.coords, "coords", (cap, 4), torch.int32), (pillars.num_points, "num_points", (cap,), torch.int32),
+               (pillars.offsets, "offsets", (B + 1,), torch.int32), (vox, "voxels", tuple(vox.shape), torch.float32))
+    for t, name, shape, _ in buffers:
+        if not torch.is_tensor(t) or tuple(t.shape) != shape:
+            raise L.MCAVError("%s: %s must be %s" % (what, name, list(shape)))
+    if need_grid and not isinstance(pillars.grid, PillarGrid):
+        raise L.MCAVError("%s: the PillarBatch has no grid (pillarize sets it)" % what)
+    device = vox.device if device is None else device
+    for t, name, _, dt in buffers:
+        if L.dev(t, name, dt).device != device:
+            raise L.MCAVError("%s: %s is on %s, the layer on %s" % (what, name, t.device, device))
+    return cap, B
+
+
+# ---------------------------------------------------------------------------------------------- the voxels' moments
+def moments_size(columns):
+    return 2 + columns + columns * columns
+
+
+def _moments_vector(t, columns, dev, what, name):
+    if not torch.is_tensor(t) or tuple(t.shape) != (moments_size(columns),) or L.dev(t, name, torch.float64).device != dev:
+        raise L.MCAVError("%s: %s must be float64 [%d] on %s" % (what, name, moments_size(columns), dev))
+    return t
+
+
+def pillar_moments(pillars, out=None):
+    """-> float64 [2 + C + C C] on the pillars' device (mcav_pillar_moments, two launches, nothing read back; the definition is
+    tests/pfn_stats_ref.py): rows = P N, used = the number of used slots, s[c] = the sum of the used slots' column c, M[c][c'] = the sum of
+    the products of their columns c and c'.  The statistics of y = W x over all P N rows of the zero-padded tensor follow from them
+    (fold_batch).  out: a tensor to fill (needed under graph capture).
+    Differentiable: with grad mode on and pillars.voxels requiring a gradient the call is a node of the autograd graph (out= is refused
+    then) whose backward is pillar_moments_backward; rows and used have no gradient."""
+    wants_grad = torch.is_grad_enabled() and isinstance(pillars, PillarBatch) and torch.is_tensor(pillars.voxels) and pillars.voxels.requires_grad
+    if wants_grad and out is not None:
+        raise L.MCAVError("pillar_moments: out= cannot be given when a gradient is required")
+    cap, B = _checked_pillars(pillars, "pillar_moments")
+    if wants_grad:
+        return _MomentsFunction.apply(pillars, pillars.voxels)
+    vox = pillars.voxels
+    N, columns, dev = vox.shape[1], vox.shape[2], vox.device
+    out = torch.empty(moments_size(columns), dtype=torch.float64, device=dev) if out is None else _moments_vector(out, columns, dev, "pillar_moments", "out")
+    hl = L.lib()
+    nbytes = hl.mcav_pillar_moments_workspace_bytes(cap, N, columns)
+    if nbytes == 0:
+        raise L.MCAVError("pillar_moments: %d rows of %d slots and %d columns are refused" % (cap, N, columns))
+    with torch.cuda.device(dev):
+        ws = L.workspace(nbytes, dev, "pfn_stats")
+        L.check(hl.mcav_pillar_moments(L.ptr(vox), L.ptr(pillars.num_points), L.ptr(pillars.offsets), B, cap, N, columns, L.ptr(out), L.ptr(ws),
+                                       nbytes, L.stream()), "mcav_pillar_moments")
+    return out
+
+
+def pillar_moments_backward(pillars, grad_moments, out=None):
+    """The backward of pillar_moments as a plain call (mcav_pillar_moments_bwd, one launch, no host synchronisation): grad_moments float64
+    [2 + C + C C], laid out as the moments are (its first two entries are not read; the part of M may be any matrix H) -> d_voxels
+    [capacity, N, C] float32, every element written: float32(g_s[c] + sum_c' (H[c][c'] + H[c'][c]) x[c']) in the used slots, +0.0 in the
+    others.  out: the tensor to fill (needed under graph capture)."""
+    cap, B = _checked_pillars(pillars, "pillar_moments_backward")
+    vox = pillars.voxels
+    N, columns, dev = vox.shape[1], vox.shape[2], vox.device
+    grad = _moments_vector(grad_moments, columns, dev, "pillar_moments_backward", "grad_moments")
+    if out is None:
+        out = torch.empty(tuple(vox.shape), dtype=torch.float32, device=dev)
+    elif not torch.is_tensor(out) or tuple(out.shape) != tuple(vox.shape) or L.dev(out, "out").device != dev:
+        raise L.MCAVError("pillar_moments_backward: out must be float32 %s on %s" % (list(vox.shape), dev))
+    with torch.cuda.device(dev):
+        L.check(L.lib().mcav_pillar_moments_bwd(L.ptr(vox), L.ptr(pillars.num_points), L.ptr(pillars.offsets), B, cap, N, columns,
+                                                L.c_p(grad.data_ptr() + 16), L.c_p(grad.data_ptr() + 8 * (2 + columns)), L.ptr(out), L.stream()),
+                "mcav_pillar_moments_bwd")
+    return out
+
+
+class _MomentsFunction(torch.autograd.Function):
+    """pillar_moments as one node: the backward is pillar_moments_backward on the saved voxels"""
+
+    @staticmethod
+    def forward(ctx, pillars, voxels):
+        ctx.pillars = pillars
+        ctx.save_for_backward(voxels)
+        return pillar_moments(pillars)                                                      # grad mode is off in here
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        voxels, = ctx.saved_tensors
+        if voxels.data_ptr() != ctx.pillars.voxels.data_ptr():
+            raise L.MCAVError("backward: the PillarBatch's voxels were replaced after the forward")
+        return None, pillar_moments_backward(ctx.pillars, grad.to(torch.float64).contiguous())
+
+
+def fold_batch(weight, gamma, beta, moments, eps, running_mean, running_var, grid=None, dtype=torch.float32):
+    """A bias-free Linear and the training-mode BatchNorm1d behind it folded into one layer, the batch statistics taken from the voxels'
+    moments: a pure function of differentiable float64 torch ops on any device, rounded once to float32 at the end.
+    weight [C_out, C or 10], gamma, beta, running_mean, running_var [C_out], moments float64 [2 + C + C C] (pillar_moments)
+    -> weight' [C_out, C], bias, bias_pad (None: the bias itself) float32; mean, var (biased) float64 [C_out] as folded; rows.
+        mean = W s / rows,  var = max(diag(W (M / rows) W^T) - mean^2, 0),  scale = gamma / sqrt(var + eps),
+        weight' = W scale,  bias = beta - mean scale
+    A 10-column weight (OpenPCDet's z - zc column, zc from `grid`) extends the 9-column moments by that column first and is collapsed to
+    nine columns as PillarFeatureNet.fold_state_dict does.  With rows < 2 there are no batch statistics (stock BatchNorm raises): the
+    running ones are folded, chosen by a torch.where on the device, and come back as mean and var.  dtype: what the folded layer is
+    rounded to (the kernels take float32; float64 leaves the fold unrounded)."""
+    w = weight.double()
+    columns = 9 if w.shape[1] == 10 else w.shape[1]
+    rows, used = moments[0], moments[1]
+    s, M = moments[2:2 + columns], moments[2 + columns:].view(columns, columns)
+    if w.shape[1] == 10:
+        if not isinstance(grid, PillarGrid):
+            raise L.MCAVError("fold_batch: a 10-column weight (z - zc) needs the PillarGrid whose z range gives zc")
+        zc = (grid.z[0] + grid.z[1]) / 2.0
+        cross = M[2] - zc * s                                                               # sum of (z - zc) x_j
+        last = M[2, 2] - 2.0 * zc * s[2] + zc * zc * used
+        s = torch.cat([s, (s[2] - zc * used)[None]])
+        M = torch.cat([torch.cat([M, cross[:, None]], dim=1), torch.cat([cross, last[None]])[None, :]], dim=0)
+    ok = rows >= 2
+    count = torch.where(ok, rows, torch.ones_like(rows))
+    batch_mean = (w @ s) / count
+    batch_var = torch.clamp(((w @ (M / count)) * w).sum(dim=1) - batch_mean * batch_mean, min=0.0)
+    mean = torch.where(ok, batch_mean, running_mean.double())
+    var = torch.where(ok, batch_var, running_var.double())
+    scale = gamma.double() / torch.sqrt(var + eps)
+    wf = w * scale[:, None]
+    bf = beta.double() + (0.0 - mean) * scale
+    if w.shape[1] != 10:
+        return wf.to(dtype).contiguous(), bf.to(dtype), None, mean, var, rows
+    bias = bf - wf[:, 9] * zc
+    wf = torch.cat([wf[:, :2], (wf[:, 2] + wf[:, 9])[:, None], wf[:, 3:9]], dim=1)
+    return wf.to(dtype).contiguous(), bias.to(dtype), bf.to(dtype), mean, var, rows
+
+
+def update_running_stats(norm, mean, var, rows):
+    """BatchNorm1d's training-mode update of `norm`'s buffers from fold_batch's mean, var (biased) and rows, in float64 device ops under
+    no_grad, nothing read back: running_mean = (1 - m) running_mean + m mean, running_var likewise with var rows / (rows - 1),
+    num_batches_tracked += 1; m = norm.momentum, or 1 / num_batches_tracked (the cumulative average) for None.  rows < 2 updates nothing."""
+    with torch.no_grad():
+        ok = rows >= 2
+        tracked = norm.num_batches_tracked + ok.to(norm.num_batches_tracked.dtype)
+        m = 1.0 / tracked.double().clamp(min=1.0) if norm.momentum is None else norm.momentum
+        unbiased = var * (rows / torch.where(ok, rows - 1.0, torch.ones_like(rows)))
+        for buf, new in ((norm.running_mean, mean), (norm.running_var, unbiased)):
+            buf.copy_(torch.where(ok, (1.0 - m) * buf.double() + m * new, buf.double()))
+        norm.num_batches_tracked.copy_(tracked)
 
 
 class PillarFeatureNet:
@@ -102,28 +265,7 @@ class PillarFeatureNet:
         return cls(*[torch.from_numpy(v).to(device) for v in cls.fold_state_dict(sd, prefix, eps, grid)])
 
     def _pillars(self, pillars, what, need_grid=False):
-        """shapes, columns and the grid first, devices and dtypes last: what can be refused without a GPU is"""
-        if not isinstance(pillars, PillarBatch):
-            raise L.MCAVError("%s: pillars must be a PillarBatch, got %r" % (what, type(pillars).__name__))
-        vox = pillars.voxels
-        if not torch.is_tensor(vox) or vox.dim() != 3 or not 1 <= vox.shape[1] <= 64:
-            raise L.MCAVError("%s: voxels must be [capacity, N <= 64, C]" % what)
-        if vox.shape[2] != self.columns:
-            raise L.MCAVError("%s: the pillars have %d columns, the layer takes %d" % (what, vox.shape[2], self.columns))
-        cap, B = vox.shape[0], len(pillars)
-        if B < 1 or cap < 1:
-            raise L.MCAVError("%s: an empty PillarBatch" % what)
-        buffers = ((pillars.coords, "coords", (cap, 4), torch.int32), (pillars.num_points, "num_points", (cap,), torch.int32),
-                   (pillars.offsets, "offsets", (B + 1,), torch.int32), (vox, "voxels", tuple(vox.shape), torch.float32))
-        for t, name, shape, _ in buffers:
-            if not torch.is_tensor(t) or tuple(t.shape) != shape:
-                raise L.MCAVError("%s: %s must be %s" % (what, name, list(shape)))
-        if need_grid and not isinstance(pillars.grid, PillarGrid):
-            raise L.MCAVError("%s: the PillarBatch has no grid (pillarize sets it)" % what)
-        for t, name, _, dt in buffers:
-            if L.dev(t, name, dt).device != self.weight.device:
-                raise L.MCAVError("%s: %s is on %s, the layer on %s" % (what, name, t.device, self.weight.device))
-        return cap, B
+        return _checked_pillars(pillars, what, self.columns, self.weight.device, need_grid)
 
     def _features_out(self, features, cap, what):
         if tuple(features.shape) != (cap, self.c_out) or L.dev(features, "features").device != self.weight.device:
@@ -274,9 +416,17 @@ class PillarFeatureLayer(torch.nn.Module):
     forward(pillars, layout) folds the BatchNorm with its RUNNING statistics into the layer in differentiable float64 torch ops
     (PillarFeatureNet.fold_state_dict's formulas, rounded once to float32) and calls PillarFeatureNet.pseudo_image, whose backward is the
     HIP kernel.  This is frozen-statistics fine-tuning: linear.weight, norm.weight and norm.bias learn; running_mean and running_var are
-    never updated, in train() as in eval(), and batch statistics over the pillars' points are not computed."""
+    never updated, in train() as in eval(), and batch statistics over the pillars' points are not computed.
 
-    def __init__(self, in_columns=9, out_channels=64, eps=1e-3, grid=None):
+    batch_stats=True makes train() what BatchNorm1d's is: forward, features and folded(pillars) take the statistics of the batch -- of
+    y = W x over all P N rows of the zero-padded voxels, as second.pytorch's masked rows give them -- from the voxels' moments
+    (pillar_moments: 2 + C + C C numbers, one pass over the used slots, no [P, N, C_out] tensor), fold them (fold_batch) and update
+    running_mean, running_var (unbiased) and num_batches_tracked as BatchNorm1d does, on the device, without a read-back; momentum=None is
+    the cumulative average.  A batch of fewer than two rows folds the running statistics and updates nothing.  The gradients of the
+    parameters flow through the statistics, and so does a second gradient of the voxels (pillar_moments_backward), which autograd adds
+    to the kernel's.  eval() is the frozen path.  The state dict does not change."""
+
+    def __init__(self, in_columns=9, out_channels=64, eps=1e-3, grid=None, batch_stats=False):
         super().__init__()
         if in_columns not in COLUMNS + (10,) or out_channels not in OUT_CHANNELS:
             raise L.MCAVError("PillarFeatureLayer: in_columns must be 4, 9 or 10 and out_channels in %s, got %r and %r"
@@ -284,11 +434,27 @@ class PillarFeatureLayer(torch.nn.Module):
         if in_columns == 10 and not isinstance(grid, PillarGrid):
             raise L.MCAVError("PillarFeatureLayer: 10 columns (z - zc) need the PillarGrid whose z range gives zc")
         self.in_columns, self.out_channels, self.eps, self.grid = in_columns, out_channels, float(eps), grid
+        self.batch_stats = bool(batch_stats)
         self.linear = torch.nn.Linear(in_columns, out_channels, bias=False)
         self.norm = torch.nn.BatchNorm1d(out_channels, eps=eps)
 
-    def folded(self):
-        """-> weight [C_out, C], bias, bias_pad (None: the bias itself) as float32 tensors with the parameters' graph behind them"""
+    def _folded_batch(self, pillars):
+        """the fold under the batch's statistics, and BatchNorm1d's update of the buffers: device ops, nothing read back"""
+        norm = self.norm
+        if not self.linear.weight.is_cuda:
+            raise L.MCAVError("PillarFeatureLayer: batch statistics need the layer on the GPU: the moments have no CPU fallback")
+        moments = pillar_moments(pillars)
+        wf, bias, bias_pad, mean, var, rows = fold_batch(self.linear.weight, norm.weight, norm.bias, moments, self.eps, norm.running_mean,
+                                                         norm.running_var, self.grid)
+        update_running_stats(norm, mean, var, rows)
+        return wf, bias, bias_pad
+
+    def folded(self, pillars=None):
+        """-> weight [C_out, C], bias, bias_pad (None: the bias itself) as float32 tensors with the parameters' graph behind them.
+        pillars: the batch whose statistics a batch_stats layer in train() folds (and updates its buffers with, once per call); without
+        them, in eval() or without batch_stats the running statistics are folded."""
+        if pillars is not None and self.batch_stats and self.training:
+            return self._folded_batch(pillars)
         w = self.linear.weight.double()
         scale = self.norm.weight.double() / torch.sqrt(self.norm.running_var.double() + self.eps)
         wf = w * scale[:, None]
@@ -302,7 +468,11 @@ class PillarFeatureLayer(torch.nn.Module):
 
     def forward(self, pillars, layout="nchw"):
         """-> the pseudo-image [B, C_out, ny, nx] of PillarFeatureNet.pseudo_image under the folded layer"""
-        return PillarFeatureNet(*self.folded()).pseudo_image(pillars, layout=layout)
+        return PillarFeatureNet(*self.folded(pillars)).pseudo_image(pillars, layout=layout)
+
+    def features(self, pillars):
+        """-> the feature rows [capacity, C_out] of PillarFeatureNet.features under the folded layer: forward without the canvas"""
+        return PillarFeatureNet(*self.folded(pillars)).features(pillars)
 
     def eval_net(self):
         """-> the PillarFeatureNet of the current parameters, without a graph"""
