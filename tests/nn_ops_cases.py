@@ -142,8 +142,49 @@ def plant_zeros(y, seed=0):
     return y
 
 
+# ------------------------------------------------------------------------------------------------ mcav_bn_eval_coeffs
+# bn_eval_coeffs_kernel: one thread per channel, 64-thread blocks, any C > 0.  1, 4: one short block; 63 / 64 / 65: on both sides of the block edge;
+# 512, 2048: the widest layers of ResNet-18 / ResNet-50 (8 and 32 blocks).
+EVAL_C = (1, 4, 63, 64, 65, 512, 2048)
+EVAL_EPS = tuple(float(np.float32(v)) for v in (1e-5, 1e-3))       # nn.BatchNorm2d's default, and one where eps decides at every small variance
+EVAL_VARS = (0.0, 1e-12, 1e-6, 1.0, 1e6)                          # running_var: exactly 0 and far below eps (eps alone), around eps, 1, huge
+# what a case fills its channels with: one running_var for all of them, `gamma` (zeros and negative values), `cancel` (|running_mean| up to 1e3
+# against a small beta, and on every other channel a beta that ALMOST equals mean * scale: shift is what is left of the two), `mixed` (all of
+# these, cycling across the channels with coprime periods)
+EVAL_KINDS = tuple("var=%g" % v for v in EVAL_VARS) + ("gamma", "cancel", "mixed")
+EVAL_CASES = [(C, kind, eps) for C in EVAL_C for kind in EVAL_KINDS for eps in EVAL_EPS]
+
+
+def eval_build(C, kind, eps, seed=0):
+    """gamma, beta, running_mean, running_var [C] float32 of one mcav_bn_eval_coeffs case (EVAL_KINDS)."""
+    g = gen(C, EVAL_KINDS.index(kind), int(round(eps * 1e6)), seed, 21)
+    gamma = (1.0 + 0.1 * torch.randn(C, generator=g)).float()
+    beta = (0.1 * torch.randn(C, generator=g)).float()
+    rm = (0.3 * torch.randn(C, generator=g)).float()
+    rv = (0.5 + torch.rand(C, generator=g)).float()
+    big = (1e3 * (0.25 + 0.75 * torch.rand(C, generator=g)) * torch.where(torch.rand(C, generator=g) < 0.5, -1.0, 1.0)).float()
+    small = (1e-3 * torch.randn(C, generator=g)).float()
+    c = torch.arange(C)
+    if kind.startswith("var="):
+        rv[:] = float(kind[4:])
+    if kind in ("gamma", "mixed"):
+        gamma[c % 3 == 1] *= -1.0
+        gamma[c % 7 == 0] = 0.0
+        gamma[c % 7 == 3] = -0.0
+    if kind == "mixed":
+        rv = torch.tensor(EVAL_VARS, dtype=F32)[c % 5].clone()
+    if kind in ("cancel", "mixed"):
+        period = 2 if kind == "cancel" else 4
+        far = c % period == 0
+        rm[far], beta[far] = big[far], small[far]
+        near = c % period == 1
+        rm[near] = big[near]
+        beta[near] = (rm[near].double() * gamma[near].double() / torch.sqrt(rv[near].double() + eps) * (1.0 + 1e-4 * torch.randn(int(near.sum()), generator=g).double())).float()
+    return dict(gamma=gamma, beta=beta, running_mean=rm, running_var=rv)
+
+
 # ------------------------------------------------------------------------------------------------ max-pool
-POOL_HW = ((1, 1), (1, 2), (2, 1), (2, 2), (3, 3), (5, 4), (7, 9), (11, 14))
+POOL_HW =((1, 1), (1, 2), (2, 1), (2, 2), (3, 3), (5, 4), (7, 9), (11, 14))
 POOL_CASES = [(B, H, W, C) for (H, W) in POOL_HW for C in (4, 64) for B in (1, 3)]
 POOL_WRAP = (1, 2049, 2049, 4)      # 1025 * 1025 outputs x one channel quad > 4096 * 256 (and four times that in the backward)
 

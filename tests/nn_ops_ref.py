@@ -37,6 +37,14 @@ def bn_finalize_ref(slab, count, gamma, beta, eps, momentum, running_mean, runni
     return dict(scale=scale, shift=shift, mean=mean, invstd=invstd, var=var, var_raw=var_raw, running_mean=rm, running_var=rv)
 
 
+def bn_eval_coeffs_ref(gamma, beta, running_mean, running_var, eps):
+    """Eval-mode BatchNorm as one multiply-add per element: y = (x - running_mean) / sqrt(running_var + eps) * gamma + beta = x * scale + shift.
+    -> (scale, shift) [C]: scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale.  running_var is a VARIANCE, eps is
+    added to it under the root, and nothing of the batch enters."""
+    scale = gamma / torch.sqrt(running_var + eps)
+    return scale, beta - running_mean * scale
+
+
 def bn_apply_ref(x, scale, shift, residual, relu, groups):
     """x: [n_pix, C], group g owns rows [g * n_pix / groups, (g + 1) * n_pix / groups); scale, shift: [groups, C].
     -> act(x * scale + shift (+ residual))."""

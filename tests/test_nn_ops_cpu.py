@@ -118,6 +118,97 @@ def test_bn_apply_and_bwd_ref_against_autograd(case):
     close(r["sums"].sum(0), torch.stack([r["dbeta"], r["dgamma"]]))
 
 
+# ------------------------------------------------------------------------------------------------ BatchNorm, eval mode
+@pytest.mark.parametrize("case", K.EVAL_CASES, ids=str)
+def test_bn_eval_coeffs_ref_against_batchnorm2d(case):
+    """x * scale + shift of bn_eval_coeffs_ref equals nn.BatchNorm2d(C).double().eval() holding the case's parameters and buffers, on a random
+    map whose channels sit around their running mean (so the two terms of the output are of one size: the cancelling case for shift)."""
+    C, kind, eps = case
+    a = K.eval_build(C, kind, eps)
+    bn = torch.nn.BatchNorm2d(C, eps=eps).double().eval()
+    with torch.no_grad():
+        bn.weight.copy_(a["gamma"]); bn.bias.copy_(a["beta"]); bn.running_mean.copy_(a["running_mean"]); bn.running_var.copy_(a["running_var"])
+    g = K.gen(C, 31)
+    x = a["running_mean"].double().view(1, C, 1, 1) + torch.sqrt(a["running_var"].double() + eps).view(1, C, 1, 1) * torch.randn(2, C, 3, 5, generator=g, dtype=F64)
+    scale, shift = R.bn_eval_coeffs_ref(a["gamma"].double(), a["beta"].double(), a["running_mean"].double(), a["running_var"].double(), eps)
+    with torch.no_grad():
+        want = bn(x)
+    got = x * scale.view(1, C, 1, 1) + shift.view(1, C, 1, 1)
+    # per element against the size of the TERMS (x * scale and shift are up to 3e5 where the output is O(1))
+    mag = (x * scale.view(1, C, 1, 1)).abs() + shift.abs().view(1, C, 1, 1) + 1e-300
+    assert float(((got - want).abs() / mag).max()) <= 1e-13
+    # and on a plain random map, against the largest output.  Not where the case plants a beta that cancels mean * scale (3e5) down to O(10):
+    # there float64 itself keeps 3e5 * 1.1e-16 = 3e-11 of the terms, 8e-12 measured against an output of 70, and the rule above is the one that holds
+    if kind not in ("cancel", "mixed"):
+        x = torch.randn(2, C, 3, 5, generator=g, dtype=F64)
+        with torch.no_grad():
+            close(x * scale.view(1, C, 1, 1) + shift.view(1, C, 1, 1), bn(x), 1e-13)
+    assert int(bn.num_batches_tracked) == 0
+
+
+def test_bn_eval_cases_cover_what_they_name():
+    """Block edge, every variance and eps, gamma zeros and negatives, |running_mean| towards 1e3 against a small beta and against a cancelling one."""
+    assert {1, 63, 64, 65, 2048} <= set(K.EVAL_C) and set(K.EVAL_EPS) == {float(np.float32(1e-5)), float(np.float32(1e-3))}
+    for C in (65, 2048):
+        for eps in K.EVAL_EPS:
+            m = K.eval_build(C, "mixed", eps)
+            assert {float(v) for v in m["running_var"]} == {float(np.float32(v)) for v in K.EVAL_VARS}
+            assert (m["gamma"] == 0).any() and (m["gamma"] < 0).any() and (m["gamma"] > 0).any()
+            for kind in ("mixed", "cancel"):
+                a = K.eval_build(C, kind, eps)
+                sc, sh = R.bn_eval_coeffs_ref(a["gamma"].double(), a["beta"].double(), a["running_mean"].double(), a["running_var"].double(), eps)
+                terms = a["beta"].double().abs() + (a["running_mean"].double() * sc).abs()
+                live = terms > 0
+                assert float(a["running_mean"].abs().max()) > 900 and float((sh.abs() / terms)[live].min()) < 1e-3      # shift cancels to 1e-4 of its terms
+                assert bool(((a["running_mean"].abs() > 250) & (a["beta"].abs() < 1e-2)).any())
+    for v in K.EVAL_VARS:
+        assert bool((K.eval_build(64, "var=%g" % v, K.EVAL_EPS[0])["running_var"] == float(np.float32(v))).all())
+
+
+def test_bn_eval_cases_have_teeth():
+    """The bound the GPU test applies (test_nn_ops_gpu.check_eval_coeffs) passes for the float32 restatement and for one that contracts
+    beta - mean * scale into a single rounding, and FAILS on at least one case for each wrong definition: eps dropped, running_var read as a
+    standard deviation, the sign of mean * scale flipped.  Checked here so that it is known without a GPU."""
+    from test_nn_ops_gpu import check_eval_coeffs
+
+    def right(g, b, m, v, eps):
+        return R.bn_eval_coeffs_ref(g, b, m, v, eps)
+
+    def contracted(g, b, m, v, eps):
+        sc = g / torch.sqrt(v + eps)
+        return sc, (b.double() - m.double() * sc.double()).float()          # one rounding for the product and the difference together
+
+    def no_eps(g, b, m, v, eps):
+        return R.bn_eval_coeffs_ref(g, b, m, v, 0.0)
+
+    def var_as_std(g, b, m, v, eps):
+        sc = g / (v + eps)
+        return sc, b - m * sc
+
+    def sign_flipped(g, b, m, v, eps):
+        sc = g / torch.sqrt(v + eps)
+        return sc, b + m * sc
+
+    def failures(f):
+        bad = []
+        for C, kind, eps in K.EVAL_CASES:
+            if C > 512:
+                continue
+            a = K.eval_build(C, kind, eps)
+            sc, sh = f(a["gamma"], a["beta"], a["running_mean"], a["running_var"], eps)
+            try:
+                check_eval_coeffs(a, eps, sc, sh)
+            except AssertionError:
+                bad.append((C, kind, eps))
+        return bad
+
+    assert failures(right) == [] and failures(contracted) == []
+    for wrong in (no_eps, var_as_std, sign_flipped):
+        bad = failures(wrong)
+        assert bad, wrong.__name__
+        print("%-12s fails %d of the cases, e.g. %s" % (wrong.__name__, len(bad), bad[0]))
+
+
 # ------------------------------------------------------------------------------------------------ max-pool
 def taps_from_flat(idx, H, W):
     """torch's flat input index (iy * W + ix, NCHW) -> tap ky * 3 + kx of the window of its output position"""

@@ -1,4 +1,4 @@
-"""GPU: the kernels of csrc/nn_ops.hip (BatchNorm finalize / apply / backward, max-pool, activation backward, layout, fused Adam) and the
+"""GPU: the kernels of csrc/nn_ops.hip (BatchNorm finalize / eval coefficients / apply / backward, max-pool, activation backward, layout, fused Adam) and the
 helpers of csrc/aux_ops.hip, each on its own through the C ABI, against the float64 definitions of tests/nn_ops_ref.py on the cases of
 tests/nn_ops_cases.py (tests/test_nn_ops_cpu.py checks those definitions against torch).
 
@@ -186,6 +186,69 @@ def test_bn_train_coeffs_wrapper_and_counter():
     assert st.groups == groups and int(bn.num_batches_tracked) == 0
     N.flush_bn_counters()
     assert int(bn.num_batches_tracked) == groups
+
+
+# ================================================================================================ mcav_bn_eval_coeffs (eval mode: scale / shift from the running statistics)
+def check_eval_coeffs(a, eps, scale, shift):
+    """scale = gamma / sqrt(running_var + eps), mag |scale|: the addition, the root, the division = 3 roundings.
+    shift = beta - running_mean * scale, mag |beta| + |running_mean * scale| (NOT the possibly cancelling difference): scale's 3, the product,
+    the subtraction and one to spare for a contracted multiply-add's other rounding = 6.  No bit equality: the device may contract.
+    (Also called by tests/test_nn_ops_cpu.py on deliberately wrong restatements: the cases must make this raise for each of them.)"""
+    gamma, beta, rm, rv = a["gamma"], a["beta"], a["running_mean"], a["running_var"]
+    sc64, sh64 = R.bn_eval_coeffs_ref(gamma.double(), beta.double(), rm.double(), rv.double(), eps)
+    sc32, sh32 = R.bn_eval_coeffs_ref(gamma, beta, rm, rv, eps)
+    three_col("eval scale", scale, sc32, sc64, sc64.abs(), 3)
+    three_col("eval shift", shift, sh32, sh64, beta.double().abs() + (rm.double() * sc64).abs(), 6)
+
+
+@pytest.mark.parametrize("case", K.EVAL_CASES, ids=str)
+def test_bn_eval_coeffs(case):
+    """Every channel written (the windows start as sentinels: a skipped one fails as NaN), nothing outside them, on both sides of the 64-thread
+    block edge and at ResNet-50's widest layer; values under the three-column rule of check_eval_coeffs."""
+    C, kind, eps = case
+    a = K.eval_build(C, kind, eps)
+    scale, shift = Guarded((C,)), Guarded((C,))
+    gamma, beta, rm, rv = (dev(a[k]) for k in ("gamma", "beta", "running_mean", "running_var"))       # (named: alive until the launch is done)
+    call("mcav_bn_eval_coeffs", P(gamma), P(beta), P(rm), P(rv), eps, C, P(scale), P(shift), outs=[scale, shift])
+    assert bool(torch.isfinite(scale.t).all()) and bool(torch.isfinite(shift.t).all())
+    check_eval_coeffs(a, eps, scale.t, shift.t)
+
+
+def test_bn_eval_coeffs_wrapper():
+    """mcav.nn.bn_eval_coeffs (the call conv_bn / tape.batchnorm make in eval mode) reads the holder's buffers as they are NOW (loaded ones too),
+    gives what the ABI gives, keeps no batch statistics (mean / invstd None: what the backward's refusal looks at) and touches no counter."""
+    from mcav import nn as N
+    from mcav.holders import BNParams
+    C, eps = 96, K.EVAL_EPS[0]
+    a = K.eval_build(C, "mixed", eps)
+    bn = BNParams(C).to(DEV)
+    assert float(np.float32(bn.eps)) == eps
+    bn.load_state_dict(dict(weight=a["gamma"], bias=a["beta"], running_mean=a["running_mean"], running_var=a["running_var"],
+                            num_batches_tracked=torch.tensor(7)))
+    N.flush_bn_counters()
+    before = {k: v.clone() for k, v in bn.state_dict().items()}
+    st = N.bn_eval_coeffs(bn)
+    torch.cuda.synchronize()
+    check_eval_coeffs(a, eps, st.scale, st.shift)
+    assert st.mean is None and st.invstd is None and st.groups == 1 and not N._NBT_PENDING
+    assert all(torch.equal(v, before[k]) for k, v in bn.state_dict().items()) and int(bn.num_batches_tracked) == 7
+
+
+def test_bn_eval_coeffs_refusals():
+    """A NULL for any of the six pointers, or C <= 0: MCAV_E_INVALID before any launch, both windows still all sentinels."""
+    C, eps = 65, K.EVAL_EPS[0]
+    a = K.eval_build(C, "mixed", eps)
+    ins = [dev(a[k]) for k in ("gamma", "beta", "running_mean", "running_var")]
+    for null in range(6):
+        scale, shift = Guarded((C,)), Guarded((C,))
+        ptrs = [P(t) for t in ins] + [P(scale), P(shift)]
+        ptrs[null] = None
+        call("mcav_bn_eval_coeffs", *ptrs[:4], eps, C, *ptrs[4:], outs=[scale, shift], expect=E_INVALID)
+        assert scale.untouched() and shift.untouched(), null
+    for bad_c in (0, -1, -64):
+        scale, shift = Guarded((C,)), Guarded((C,))
+        call("mcav_bn_eval_coeffs", *[P(t) for t in ins], eps, bad_c, P(scale), P(shift), outs=[scale, shift], expect=E_INVALID)
+        assert scale.untouched() and shift.untouched(), bad_c
 
 
 # ================================================================================================ 3.3 apply, backward reduce + finalize, backward apply

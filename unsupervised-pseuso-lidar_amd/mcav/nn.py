@@ -1010,6 +1010,18 @@ def flush_bn_counters():
         _NBT_PENDING.clear()
 
 
+EVAL_BACKWARD_REFUSED = ("backward through an eval-mode BatchNorm: the forward ran on the running statistics and saved no batch statistics "
+                         "(call .train() before a forward that is to be differentiated)")
+
+
+def refuse_eval_backward(st):
+    """The networks call this at the FRONT of their backward with a BatchNorm state of the forward: an eval-mode one (no saved mean) is refused
+    here, on the host, before the first launch -- not half-way, after the layers behind the first BatchNorm have accumulated their gradients
+    and the weight-gradient stream has forked (mcav_bn_bwd_reduce would return MCAV_E_INVALID on the NULL statistic there)."""
+    if st.mean is None:
+        raise L.MCAVError(EVAL_BACKWARD_REFUSED)
+
+
 def bn_eval_coeffs(bn):
     C = bn.weight.shape[0]
     st = BNState()

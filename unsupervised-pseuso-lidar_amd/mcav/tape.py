@@ -29,6 +29,7 @@ class Tape:
         self.steps = []
         self.grads = {}
         self.enabled = enabled
+        self.refusal = None         # why this tape cannot run backwards (an eval-mode BatchNorm keeps no batch statistics), checked before any step
 
     def record(self, fn):
         if self.enabled:
@@ -44,6 +45,8 @@ class Tape:
 
     def backward(self, seeds):
         """seeds: list of (tensor, gradient)."""
+        if self.refusal is not None:            # before the first step: nothing launched, no gradient touched, no stream forked
+            raise L.MCAVError(self.refusal)
         for t, g in seeds:
             self.add_grad(t, g)
         for fn in reversed(self.steps):
@@ -132,6 +135,7 @@ def batchnorm(tape, bn, x, slab, train):
         st = N.bn_train_coeffs(bn, slab, x.shape[0] * x.shape[1] * x.shape[2])
     else:
         st = N.bn_eval_coeffs(bn)
+        tape.refusal = N.EVAL_BACKWARD_REFUSED
     y = N.bn_apply(x, st, False)
 
     def bwd():

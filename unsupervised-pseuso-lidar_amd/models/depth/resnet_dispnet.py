@@ -92,6 +92,7 @@ class _EncoderFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gfeats):
+        N.refuse_eval_backward(ctx.sv["st"])
         dfe = [N.nchw_to_nhwc(L.dev(g.contiguous(), "grad"), g.shape[1]) for g in gfeats]
         E.encoder_backward(ctx.mod.encoder, ctx.sv, dfe)
         return (None, None) + (None,) * len(list(ctx.mod.parameters()))
@@ -213,6 +214,7 @@ class _DispResNetFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gs):
         mod = ctx.mod
+        N.refuse_eval_backward(ctx.esv["st"])            # before the decoder's gradients are accumulated
         dfe = E.decoder_backward(mod.decoder, ctx.dsv, _head_grads(ctx.scales, gs))
         E.encoder_backward(mod.encoder.encoder, ctx.esv, dfe)
         ctx.esv = ctx.dsv = None
@@ -248,6 +250,7 @@ class _DispResNetPairFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *gs):
         mod = ctx.mod
+        N.refuse_eval_backward(ctx.esv["st"])
         n = len(ctx.scales)
         stacked = []
         for ga, gb in zip(gs[:n], gs[n:]):
