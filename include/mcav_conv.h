@@ -68,7 +68,10 @@ typedef struct mcav_igemm_desc {
     int pool;               /* 1: destination pixels are visited in 2x2 blocks and summed: y is [B, Hd/2, Wd/2, Cd] */
     float* stats;           /* NULL or [mtiles][2][n_count]: per-tile column sums of y and y^2 (BatchNorm batch statistics) */
     int tile;               /* 0 = choose automatically; else a tile-config id in the low byte; bits 8-16 = test / tuning switches that force or forbid one
-                             * of the kernel forms (bit 13: the fp32 patch-in-LDS kernel for 3x3 stride-1 zero-padded launches; bit 14: the second
+                             * of the kernel forms (bit 8: the general gather instead of the offset-table kernel; bit 9: the general kernels -- no
+                             * halo kernel, no stem kernel; bit 10: the halo kernels keep their 9-tap form on an upsampled source; bits 11 and 12
+                             * are read by the host package only, where it chooses between a launch and its merged-tap form (mcav/nn.py:
+                             * TILE_NO_UPMERGE, TILE_ALT_UPMERGE); bit 13: the fp32 patch-in-LDS kernel for 3x3 stride-1 zero-padded launches; bit 14: the second
                              * patch kernel of the split form -- 128- / 256-row tiles, LDS-DMA filter ring, one workgroup per CU --, bit 15: its
                              * 128 x 32 configuration at two workgroups per CU; bit 16: the depth stem with the shared 4-byte-store epilogue) */
     int groups;             /* 0/1 = one group.  G > 1: the batch is G equal groups (e.g. the tgt and ref0 passes of the depth net run as

@@ -52,41 +52,47 @@ def block_forward(blk, x, stride, train, groups=1):
     return sv["out"], sv
 
 
-def block_backward(blk, sv, dout, addend=None, fused_in=None, consumer=None):
-    """fused_in: (slab, tiles per group) when `dout` already carries this block's bn2 ReLU mask and partial sums (produced by the previous
-    call's last data gradient).  consumer: saved tensors of the block that will receive this call's result, when that gradient may carry
-    ITS last BatchNorm's mask and partial sums (same stage, stride-1 first conv here) -> returns (dx, (slab, tiles per group))."""
-    x, stride = sv["x"], sv["stride"]
-    c1 = spec_of(blk.conv1, stride, 1, N.PAD_ZERO)
-    c2 = spec_of(blk.conv2, 1, 1, N.PAD_ZERO)
-    dr2, dz = N.bn_backward(blk.bn2, sv["st2"], dout, sv["out"], sv["r2"], True, want_dres=True, fused=fused_in)
-    N.conv_wgrad(c2, sv["h1"], dr2)
-    if N.can_fuse_bn_stats(c2) and sv["st1"].mean is not None:
-        # dh1 arrives masked by ReLU'(h1) with bn1's backward partial sums in the epilogue's slab: no reduce pass over dh1 / h1 / r1
-        dh1, slab, mtg = N.conv_dgrad(c2, dr2, hw(sv["h1"]), dact_aux=sv["h1"], dact=N.ACT_RELU, bn_stats=(sv["r1"], sv["st1"]))
-        dr1 = N.bn_backward(blk.bn1, sv["st1"], dh1, None, sv["r1"], True, fused=(slab, mtg))
-    else:
-        dh1 = N.conv_dgrad(c2, dr2, hw(sv["h1"]))
-        dr1 = N.bn_backward(blk.bn1, sv["st1"], dh1, sv["h1"], sv["r1"], True)
+def _dgrad_through_bn(spec, dy, h, raw, st, bn):
+    """Gradient at a BatchNorm's raw input from dy, the gradient at the output of the convolution `spec` that reads h = relu(bn(raw))."""
+    if N.can_fuse_bn_stats(spec) and st.mean is not None:
+        # dh arrives masked by ReLU'(h) with the BatchNorm's backward partial sums in the epilogue's slab: no reduce pass over dh / h / raw
+        dh, slab, mtg = N.conv_dgrad(spec, dy, hw(h), dact_aux=h, dact=N.ACT_RELU, bn_stats=(raw, st))
+        return N.bn_backward(bn, st, dh, None, raw, True, fused=(slab, mtg))
+    return N.bn_backward(bn, st, N.conv_dgrad(spec, dy, hw(h)), h, raw, True)
+
+
+def _block_tail(blk, sv, c1, dr1, dz, addend, consumer, last):
+    """The end of a residual block's backward: conv1's weight and data gradient, joined by the shortcut's gradient dz (through the downsample
+    branch where there is one).  last = (raw output, BatchNorm state) keys of the consumer's last BatchNorm.  -> (dx, (slab, tiles per group) or None)"""
+    x = sv["x"]
     N.conv_wgrad(c1, x, dr1)
-    out_stats = None
     kw = {}
-    if consumer is not None and N.can_fuse_bn_stats(c1) and consumer["st2"].mean is not None:
+    if consumer is not None and N.can_fuse_bn_stats(c1) and consumer[last[1]].mean is not None:
         # the consumer's output ReLU masks the SUM of this gradient and the residual branch's (the addend)
-        kw = dict(dact_aux=consumer["out"], dact=N.ACT_RELU | N.DACT_AFTER_ADDEND, bn_stats=(consumer["r2"], consumer["st2"]))
+        kw = dict(dact_aux=consumer["out"], dact=N.ACT_RELU | N.DACT_AFTER_ADDEND, bn_stats=(consumer[last[0]], consumer[last[1]]))
     if blk.downsample is None:
         if addend is not None:
             dz = N.add(dz, addend)
         res = N.conv_dgrad(c1, dr1, hw(x), addend=dz, **kw)
     else:
-        cd = spec_of(blk.downsample[0], stride, 0, N.PAD_ZERO)
+        cd = spec_of(blk.downsample[0], sv["stride"], 0, N.PAD_ZERO)
         drd = N.bn_backward(blk.downsample[1], sv["std"], dz, None, sv["rd"], False)
         N.conv_wgrad(cd, x, drd)
         dxd = N.conv_dgrad(cd, drd, hw(x), addend=addend)
         res = N.conv_dgrad(c1, dr1, hw(x), addend=dxd, **kw)
-    if kw:
-        return res[0], (res[1], res[2])
-    return res, None
+    return (res[0], (res[1], res[2])) if kw else (res, None)
+
+
+def block_backward(blk, sv, dout, addend=None, fused_in=None, consumer=None):
+    """fused_in: (slab, tiles per group) when `dout` already carries this block's bn2 ReLU mask and partial sums (produced by the previous
+    call's last data gradient).  consumer: saved tensors of the block that will receive this call's result, when that gradient may carry
+    ITS last BatchNorm's mask and partial sums (same stage, stride-1 first conv here) -> returns (dx, (slab, tiles per group))."""
+    c1 = spec_of(blk.conv1, sv["stride"], 1, N.PAD_ZERO)
+    c2 = spec_of(blk.conv2, 1, 1, N.PAD_ZERO)
+    dr2, dz = N.bn_backward(blk.bn2, sv["st2"], dout, sv["out"], sv["r2"], True, want_dres=True, fused=fused_in)
+    N.conv_wgrad(c2, sv["h1"], dr2)
+    dr1 = _dgrad_through_bn(c2, dr2, sv["h1"], sv["r1"], sv["st1"], blk.bn1)
+    return _block_tail(blk, sv, c1, dr1, dz, addend, consumer, ("r2", "st2"))
 
 
 # ------------------------------------------------------------------------------------------------ Bottleneck (ResNet-50/101/152)
@@ -106,42 +112,15 @@ def bottleneck_forward(blk, x, stride, train, groups=1):
 def bottleneck_backward(blk, sv, dout, addend=None, fused_in=None, consumer=None):
     """As block_backward; the BatchNorms whose incoming gradient a stride-1 data gradient produces (bn2 after the 1x1 conv3, bn1 after a
     stride-1 conv2, the consumer block's bn3 after this block's 1x1 conv1) take their backward partial sums from that launch's epilogue."""
-    x, stride = sv["x"], sv["stride"]
     c1 = spec_of(blk.conv1, 1, 0, N.PAD_ZERO)
-    c2 = spec_of(blk.conv2, stride, 1, N.PAD_ZERO)
+    c2 = spec_of(blk.conv2, sv["stride"], 1, N.PAD_ZERO)
     c3 = spec_of(blk.conv3, 1, 0, N.PAD_ZERO)
     dr3, dz = N.bn_backward(blk.bn3, sv["st3"], dout, sv["out"], sv["r3"], True, want_dres=True, fused=fused_in)
     N.conv_wgrad(c3, sv["h2"], dr3)
-    if N.can_fuse_bn_stats(c3) and sv["st2"].mean is not None:
-        dh2, slab, mtg = N.conv_dgrad(c3, dr3, hw(sv["h2"]), dact_aux=sv["h2"], dact=N.ACT_RELU, bn_stats=(sv["r2"], sv["st2"]))
-        dr2 = N.bn_backward(blk.bn2, sv["st2"], dh2, None, sv["r2"], True, fused=(slab, mtg))
-    else:
-        dh2 = N.conv_dgrad(c3, dr3, hw(sv["h2"]))
-        dr2 = N.bn_backward(blk.bn2, sv["st2"], dh2, sv["h2"], sv["r2"], True)
+    dr2 = _dgrad_through_bn(c3, dr3, sv["h2"], sv["r2"], sv["st2"], blk.bn2)
     N.conv_wgrad(c2, sv["h1"], dr2)
-    if N.can_fuse_bn_stats(c2) and sv["st1"].mean is not None:
-        dh1, slab, mtg = N.conv_dgrad(c2, dr2, hw(sv["h1"]), dact_aux=sv["h1"], dact=N.ACT_RELU, bn_stats=(sv["r1"], sv["st1"]))
-        dr1 = N.bn_backward(blk.bn1, sv["st1"], dh1, None, sv["r1"], True, fused=(slab, mtg))
-    else:
-        dh1 = N.conv_dgrad(c2, dr2, hw(sv["h1"]))
-        dr1 = N.bn_backward(blk.bn1, sv["st1"], dh1, sv["h1"], sv["r1"], True)
-    N.conv_wgrad(c1, x, dr1)
-    kw = {}
-    if consumer is not None and N.can_fuse_bn_stats(c1) and consumer["st3"].mean is not None:
-        kw = dict(dact_aux=consumer["out"], dact=N.ACT_RELU | N.DACT_AFTER_ADDEND, bn_stats=(consumer["r3"], consumer["st3"]))
-    if blk.downsample is None:
-        if addend is not None:
-            dz = N.add(dz, addend)
-        res = N.conv_dgrad(c1, dr1, hw(x), addend=dz, **kw)
-    else:
-        cd = spec_of(blk.downsample[0], stride, 0, N.PAD_ZERO)
-        drd = N.bn_backward(blk.downsample[1], sv["std"], dz, None, sv["rd"], False)
-        N.conv_wgrad(cd, x, drd)
-        dxd = N.conv_dgrad(cd, drd, hw(x), addend=addend)
-        res = N.conv_dgrad(c1, dr1, hw(x), addend=dxd, **kw)
-    if kw:
-        return res[0], (res[1], res[2])
-    return res, None
+    dr1 = _dgrad_through_bn(c2, dr2, sv["h1"], sv["r1"], sv["st1"], blk.bn1)
+    return _block_tail(blk, sv, c1, dr1, dz, addend, consumer, ("r3", "st3"))
 
 
 # ------------------------------------------------------------------------------------------------ encoder

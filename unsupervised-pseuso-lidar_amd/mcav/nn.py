@@ -18,6 +18,13 @@ G_DIRECT, G_SMALLC, G_ADJ_REFLECT, G_ADJ_STRIDE2 = 0, 1, 2, 3
 PAD_ZERO, PAD_REFLECT = 0, 1
 ACT_NONE, ACT_RELU, ACT_ELU, ACT_SIGMOID = 0, 1, 2, 3
 DACT_AFTER_ADDEND = 0x100       # (conv + addend) * act'(aux) instead of conv * act'(aux) + addend
+# mcav_*_desc.tile / the `tile` argument of conv_fwd, conv_dgrad, conv_wgrad: a tile-config id and the test / tuning switches this module reads
+TILE_ID_MASK = 0xff             # the tile-config id (0 = chosen by the planner); all that the merged upsample adjoint's launch is given
+TILE_GENERAL = 1 << 9           # the general kernels: no patch-in-LDS stem kernel (and no w_stem, no planar source), no halo kernel
+TILE_HALO_9TAP = 1 << 10        # the halo kernels keep their 9-tap form on an upsampled source (read by the planner only)
+TILE_NO_UPMERGE = 1 << 11       # conv(cat(up2(x1), x2)): no merged-tap filter copy in the forward, one ordinary weight-gradient launch
+TILE_ALT_UPMERGE = 1 << 12      # the other merged-tap choice: the two-launch weight gradient also at 32 outputs, the pooled 9-tap data gradient
+                                # instead of the merged 4x4 stride-2 adjoint
 
 
 class IgemmDesc(ctypes.Structure):
@@ -162,13 +169,13 @@ class _Timed:
     """flops: the reference's algorithmic FLOPs of the launch (2 M N K of the convolution it stands for).  executed: what the MFMA pipe really
     does -- less for the merged-tap forms (4 taps instead of 9 on the upsampled half), more where K is padded (the stem's 168 k for 147)."""
 
-    def __init__(self, kind, flops, tag="", executed=None, bf16_planes=0, abytes=0.0):
-        """bf16_planes: plane products per algorithmic product when the launch runs on the bf16 MFMA pipe (1 = plain bf16, 6 = the fp32
-        contraction on split operands), 0 = an fp32-MFMA (or non-MFMA) launch.  abytes: the launch's ALGORITHMIC bytes -- every operand
-        read once, the result written once, fp32 (the per-launch roofline is min(MFMA peak, flops / abytes x HBM peak))."""
-        self.kind, self.flops, self.tag = kind, flops, tag
-        self.executed = flops if executed is None else executed
-        self.bf16_planes, self.abytes = bf16_planes, abytes
+    def __init__(self, kind, account):
+        """account: () -> (flops, tag, executed or None = flops, bf16_planes, abytes), asked only when PROFILE is a list (an eager step pays
+        for no accounting).  bf16_planes: plane products per algorithmic product when the launch runs on the bf16 MFMA pipe (1 = plain
+        bf16, 6 = the fp32 contraction on split operands), 0 = an fp32-MFMA (or non-MFMA) launch.  abytes: the launch's ALGORITHMIC bytes --
+        every operand read once, the result written once, fp32 (the per-launch roofline is min(MFMA peak, flops / abytes x
+        HBM peak))."""
+        self.kind, self.account = kind, account
 
     def __enter__(self):
         if PROFILE is not None:
@@ -177,10 +184,24 @@ class _Timed:
 
     def __exit__(self, *exc):
         if PROFILE is not None:
-            PROFILE.append(ProfileRec(self.kind, self.flops, self.i0, L.lib().mcav_kernel_timer_count(), self.executed, self.bf16_planes, self.abytes))
+            flops, tag, executed, planes, abytes = self.account()
+            PROFILE.append(ProfileRec(self.kind, flops, self.i0, L.lib().mcav_kernel_timer_count(), flops if executed is None else executed, planes, abytes))
             if PROFILE_TAGS is not None:
-                PROFILE_TAGS.append(self.tag)
+                PROFILE_TAGS.append(tag)
         return False
+
+
+def _planned(d):
+    """The route the planner gives a filled IgemmDesc / WgradDesc (asked by the accounting: which form a launch takes is the planner's to say).
+    A descriptor it refuses leaves the route zeroed; the launch itself reports the refusal."""
+    r = ConvRoute()
+    (L.lib().mcav_igemm_route if isinstance(d, IgemmDesc) else L.lib().mcav_wgrad_route)(ctypes.byref(d), ctypes.byref(r))
+    return r
+
+
+def _stem_executed(flops, cout):
+    """What the MFMA pipe does in a stem kernel: the K order pads 7 filter columns to 8, and 16 outputs use half of a 32-wide tile."""
+    return flops * (8.0 / 7.0) * (1.0 if cout >= 32 else 2.0)
 
 
 def up16(v):
@@ -353,6 +374,14 @@ class ConvSpec:
         return ((self.kh, self.kw, self.stride, self.pad, self.pad_mode) == (7, 7, 2, 3, PAD_ZERO)
                 and ((self.smallc and (self.cout, self.cin) == (64, 3)) or (not self.smallc and (self.cout, self.cin) == (16, 9))))
 
+    def takes_stem(self, x2, up1, tile):
+        """A forward-gather launch (conv_fwd, conv_wgrad) of this convolution on these sources goes to the stem kernels."""
+        return self.is_stem() and x2 is None and not up1 and not tile & TILE_GENERAL
+
+    def fwd_gather(self):
+        """(mode, stride, sign, offset, pad_mode) of the forward launch and of the weight gradient, which gathers the same source."""
+        return (G_SMALLC if self.smallc else G_DIRECT, self.stride, 1, -self.pad, self.pad_mode)
+
     def packed_stem(self):
         """[Cin * 56][Cout] copy of a stem filter in the K order of csrc/conv_stem.hip (mcav_pack_stem_weights); one tiny launch when stale."""
         key = self._key()
@@ -485,20 +514,70 @@ def stats_blocks_stem(spec, stats):
     return stats and not spec.smallc           # (only the image stem's kernel carries the BatchNorm statistics epilogue)
 
 
-def _weights_for(spec, d, transposed):
-    """Fills d.w / d.w16 / d.mma of an IgemmDesc whose geometry is already set: the bf16 copy where the launch runs on the bf16 kernels."""
+def _gather_source(x1, x2, up1, takes_stem, planar_launch):
+    """The source of a forward-gather launch (conv_fwd, conv_wgrad) -> (x1, (B, Hs, Ws, C1, C2, up1) of the logical source).  Only the stem
+    kernels read planar images where they are: for any other launch they are packed first."""
+    if isinstance(x1, PlanarImages):
+        if takes_stem:
+            LAUNCHES[planar_launch] += 1
+        else:
+            x1 = x1.packed()
+    B, H, W, C1 = x1.shape
+    return x1, (B, 2 * H if up1 else H, 2 * W if up1 else W, C1, x2.shape[3] if x2 is not None else 0, int(up1))
+
+
+def _set_source(d, x1, x2, source, gather):
+    """The fields mcav_igemm_desc and mcav_wgrad_desc share: source = (B, Hs, Ws, C1, C2, up1), gather = (mode, stride, sign, offset, pad_mode)."""
+    if isinstance(x1, PlanarImages):
+        x1.fill(d)
+    else:
+        d.x1 = P(x1)
+    d.x2 = P(x2)
+    d.B, d.Hs, d.Ws, d.C1, d.C2, d.up1 = source
+    d.mode, d.stride, d.sign, d.offset, d.pad_mode = gather
+    return d
+
+
+def _igemm_desc(x1, x2, source, filt, gather, y, dest, tile=0):
+    """filt = (kh, kw, Np, Kp); dest = (Hd, Wd, n_begin, n_count) of the window of y's channels the launch writes.  The filter pointers and
+    the epilogue are the caller's."""
+    d = _set_source(IgemmDesc(), x1, x2, source, gather)
+    d.kh, d.kw, d.Np, d.Kp = filt
+    d.y, d.Cd = P(y), y.shape[3]
+    d.Hd, d.Wd, d.n_begin, d.n_count = dest
+    d.tile = tile
+    return d
+
+
+def _wgrad_desc(x1, x2, source, filt, gather, dy, cout, cin, gw, gb, tile=0, mma=0):
+    """filt = (kh, kw, Kp); dy: the gradient at the output, all of its channels; gw / gb: where the OIHW gradient and the bias gradient are
+    accumulated."""
+    d = _set_source(WgradDesc(), x1, x2, source, gather)
+    d.kh, d.kw, d.Kp = filt
+    d.dy, d.Hd, d.Wd, d.Cdy = P(dy), dy.shape[1], dy.shape[2], dy.shape[3]
+    d.Cout, d.Cin = cout, cin
+    d.dw_oihw, d.accumulate, d.dbias = P(gw), 1, P(gb)
+    d.tile, d.mma = tile, mma
+    return d
+
+
+def _weights_for(spec, d, transposed, fp32=None, bf16=None):
+    """Fills d.w / d.w16 / d.mma of an IgemmDesc whose geometry is already set: the bf16 copy where the launch runs on the bf16 kernels.
+    fp32 / bf16: () -> the fp32 filter and (planes) -> its bf16 copy, for a launch that does not take the spec's packed copies (the merged
+    upsample adjoint: its bf16 copy is converted from the fp32 one, which is therefore made first and stays in d.w)."""
+    given = P(fp32()) if fp32 is not None else None
+    if fp32 is None:
+        fp32 = spec.packed_bwd if transposed else spec.packed_fwd
+        bf16 = lambda planes: getattr(spec, "packed_%s16%s" % ("bwd" if transposed else "fwd", "s" if planes == 3 else ""))()
     if spec.mma in (MMA_BF16, MMA_SPLIT, MMA_SPLIT_ALL):
         ph = d.x1 or d.x_planar[0]
         d.mma, d.w16, d.w = spec.mma, ph, ph              # placeholders: the eligibility test looks at the geometry only
         if L.lib().mcav_igemm_uses_bf16(ctypes.byref(d)):
-            if spec.mma >= MMA_SPLIT:
-                w16 = spec.packed_bwd16s() if transposed else spec.packed_fwd16s()
-            else:
-                w16 = spec.packed_bwd16() if transposed else spec.packed_fwd16()
-            d.w16 = d.w = P(w16)                           # (w is never read on the bf16 path; it only has to be non-null)
+            d.w16 = P(bf16(3 if spec.mma >= MMA_SPLIT else 1))
+            d.w = given or d.w16                           # (w is never read on the bf16 path; it only has to be non-null)
             return
     d.mma, d.w16 = 0, None
-    d.w = P(spec.packed_bwd() if transposed else spec.packed_fwd())
+    d.w = given or P(fp32())
 
 
 def _planes(d):
@@ -516,58 +595,42 @@ def out_size(n, k, s, p):
 
 def conv_fwd(spec, x1, x2=None, up1=False, act=ACT_NONE, stats=False, tile=0, groups=1):
     """y = act(conv(cat(up2?(x1), x2)) + bias).  x1/x2 NHWC.  Returns y, or (y, stats_slab, mtiles) when stats."""
-    takes_stem = spec.is_stem() and not stats_blocks_stem(spec, stats) and x2 is None and not up1 and not (tile >> 9) & 1
-    planar = x1 if isinstance(x1, PlanarImages) else None
-    if planar is not None and not takes_stem:
-        x1, planar = planar.packed(), None
-    B = x1.shape[0]
-    Hs, Ws = (x1.shape[1] * 2, x1.shape[2] * 2) if up1 else (x1.shape[1], x1.shape[2])
-    C1 = x1.shape[3]
-    C2 = x2.shape[3] if x2 is not None else 0
+    takes_stem = spec.takes_stem(x2, up1, tile) and not stats_blocks_stem(spec, stats)
+    x1, source = _gather_source(x1, x2, up1, takes_stem, "fwd_planar")
+    B, Hs, Ws, C1 = source[:4]
     Hd, Wd = out_size(Hs, spec.kh, spec.stride, spec.pad), out_size(Ws, spec.kw, spec.stride, spec.pad)
     y = empty((B, Hd, Wd, spec.cout), x1)
-    d = IgemmDesc()
-    if planar is not None:
-        planar.fill(d)
-        LAUNCHES["fwd_planar"] += 1
-    else:
-        d.x1 = P(x1)
-    d.x2 = P(x2)
-    d.B, d.Hs, d.Ws, d.C1, d.C2, d.up1 = B, Hs, Ws, C1, C2, int(up1)
-    d.kh, d.kw, d.Np, d.Kp = spec.kh, spec.kw, spec.np, spec.kp
-    d.mode = G_SMALLC if spec.smallc else G_DIRECT
-    d.stride, d.sign, d.offset, d.pad_mode = spec.stride, 1, -spec.pad, spec.pad_mode
-    d.y, d.Hd, d.Wd, d.Cd, d.n_begin, d.n_count, d.y_choff = P(y), Hd, Wd, spec.cout, 0, spec.cout, 0
+    d = _igemm_desc(x1, x2, source, (spec.kh, spec.kw, spec.np, spec.kp), spec.fwd_gather(), y, (Hd, Wd, 0, spec.cout), tile)
     d.bias, d.act = P(spec.bias), act
-    d.tile = tile
     d.groups = groups if stats else 1
     _weights_for(spec, d, False)
     if takes_stem:
-        d.w_stem = P(spec.packed_stem())               # a 7x7 stride-2 stem: patch-in-LDS kernel (tile bit 9 keeps the general one)
+        d.w_stem = P(spec.packed_stem())               # a 7x7 stride-2 stem: patch-in-LDS kernel
         if spec.mma == MMA_SPLIT_ALL and spec.smallc and spec.cout == 64:
             d.mma = spec.mma                           # the depth stem in the split form (stem7x7s2_split_fwd_kernel splits the packed fp32 slice itself): level with
                                                        # the fp32 stem kernel, so only "every launch on the split kernels" (the parity tests) takes it
     if (up1 and x2 is not None and not stats and spec.kh == 3 and spec.kw == 3 and spec.stride == 1 and spec.pad == 1
-            and spec.pad_mode == PAD_REFLECT and C1 % 16 == 0 and not (tile >> 11) & 1 and not d.mma):
-        d.w_upmerge = P(spec.packed_upmerge(C1))       # the upsampled part as 4 merged taps on the low-resolution x1 (tile bit 11: off)
-    h = L.lib()
+            and spec.pad_mode == PAD_REFLECT and C1 % 16 == 0 and not tile & TILE_NO_UPMERGE and not d.mma):
+        d.w_upmerge = P(spec.packed_upmerge(C1))       # the upsampled part as 4 merged taps on the low-resolution x1
     slab = None
     if stats:
-        mt = h.mcav_igemm_mtiles(ctypes.byref(d))
+        mt = L.lib().mcav_igemm_mtiles(ctypes.byref(d))
         if mt <= 0:
             raise L.MCAVError("mcav_igemm_mtiles: invalid descriptor (%d)" % mt)
         slab = empty((mt, 2, spec.cout), x1)
         d.stats = P(slab)
-    flops = 2.0 * B * Hd * Wd * spec.cout * spec.cin * spec.kh * spec.kw
-    executed = flops
-    if d.w_upmerge or (up1 and x2 is None and spec.kh == 3 and spec.pad_mode == PAD_REFLECT and C1 in (16, 32) and spec.cout <= 32
-                       and not (tile >> 10) & 1 and not (tile >> 9) & 1):
-        executed = flops * ((4.0 / 9.0) * C1 + C2) / (C1 + C2)          # upsampled source: 4 merged taps instead of 9 (table kernel / halo kernel)
-    if d.w_stem:
-        executed = flops * (8.0 / 7.0) * (1.0 if spec.cout >= 32 else 2.0)  # the stem's K order pads 7 columns to 8; 16 outputs use half a 32-wide tile
-    abytes = 4.0 * (x1.numel() + (x2.numel() if x2 is not None else 0) + y.numel() + spec.weight.numel())
-    with _Timed("fwd", flops, "M=%d N=%d K=%dx%d s%d %dx%d%s" % (B * Hd * Wd, spec.cout, spec.cin, spec.kh * spec.kw, spec.stride, Hd, Wd, _pipe_tag(d)),
-                executed, _planes(d), abytes):
+
+    def account():
+        flops = 2.0 * B * Hd * Wd * spec.cout * spec.cin * spec.kh * spec.kw
+        r = _planned(d)
+        executed = flops
+        if r.variant & RV_UPM:                         # upsampled source: 4 merged taps instead of 9 (table kernel / halo kernel)
+            executed = flops * ((4.0 / 9.0) * C1 + d.C2) / (C1 + d.C2)
+        if r.family == IGEMM_STEM:
+            executed = _stem_executed(flops, spec.cout)
+        return (flops, "M=%d N=%d K=%dx%d s%d %dx%d%s" % (B * Hd * Wd, spec.cout, spec.cin, spec.kh * spec.kw, spec.stride, Hd, Wd, _pipe_tag(d)),
+                executed, _planes(d), 4.0 * (x1.numel() + (x2.numel() if x2 is not None else 0) + y.numel() + spec.weight.numel()))
+    with _Timed("fwd", account):
         _launch_igemm(d, "fwd")
     return (y, slab) if stats else y
 
@@ -581,6 +644,10 @@ def can_fuse_bn_stats(spec):
     return BN_BWD_FUSE and spec.stride == 1 and spec.pad_mode == PAD_ZERO
 
 
+# (stride, pad_mode) of a convolution -> (mode, stride, sign, offset) of its data gradient's gather; offset None: the convolution's padding
+_DGRAD_GATHER = {(1, PAD_REFLECT): (G_ADJ_REFLECT, 1, -1, 1), (1, PAD_ZERO): (G_DIRECT, 1, -1, None), (2, PAD_ZERO): (G_ADJ_STRIDE2, 2, -1, None)}
+
+
 def conv_dgrad(spec, dy, in_shape, n_begin=0, n_count=None, out=None, dact_aux=None, dact=ACT_NONE, addend=None, pool=False, tile=0, bn_stats=None):
     """Gradient w.r.t. the (logical, concatenated) conv input, channels [n_begin, n_begin + n_count).
 
@@ -588,33 +655,21 @@ def conv_dgrad(spec, dy, in_shape, n_begin=0, n_count=None, out=None, dact_aux=N
     Epilogue: 2x2 sum pooling (pool), * act'(dact_aux), + addend.  Returns [B, Hs(/2), Ws(/2), n_count].
     bn_stats = (x_raw, BNState): the result is the gradient arriving at a train-mode BatchNorm whose raw input was x_raw; the epilogue also
     leaves that BatchNorm's backward partial sums (sum g, sum g * xhat per tile and channel) in a slab -> returns (y, slab, tiles per group)."""
-    B, Hd, Wd, Cout = dy.shape
+    B, Hd, Wd, Cout = dy.shape                      # Cout = channels physically in dy (may be zero-padded past spec.cout)
     Hs, Ws = in_shape
     if n_count is None:
         n_count = spec.cin
     if (pool and n_begin == 0 and out is None and spec.kh == 3 and spec.kw == 3 and spec.stride == 1 and spec.pad == 1
             and spec.pad_mode == PAD_REFLECT and n_count % 16 == 0 and n_count >= UPMERGE_ADJ_MIN_N and Cout == up16(spec.cout)
-            and Cout % 32 == 0 and Hs % 2 == 0 and Ws % 2 == 0 and not (tile >> 12) & 1):
+            and Cout % 32 == 0 and Hs % 2 == 0 and Ws % 2 == 0 and not tile & TILE_ALT_UPMERGE):
         return _dgrad_upsample_merged(spec, dy, (Hs, Ws), n_count, dact_aux, dact, addend, tile)
     y = out if out is not None else empty((B, Hs // 2 if pool else Hs, Ws // 2 if pool else Ws, n_count), dy)
-    d = IgemmDesc()
-    d.x1, d.x2 = P(dy), None
-    d.B, d.Hs, d.Ws, d.C1, d.C2, d.up1 = B, Hd, Wd, Cout, 0, 0       # Cout = channels physically in dy (may be zero-padded past spec.cout)
-    d.kh, d.kw, d.Np, d.Kp = spec.kh, spec.kw, up16(spec.cin), up16(spec.cout)
-    if spec.stride == 1:
-        if spec.pad_mode == PAD_REFLECT:
-            d.mode, d.stride, d.sign, d.offset = G_ADJ_REFLECT, 1, -1, 1
-        else:
-            d.mode, d.stride, d.sign, d.offset = G_DIRECT, 1, -1, spec.pad
-    elif spec.stride == 2 and spec.pad_mode == PAD_ZERO:
-        d.mode, d.stride, d.sign, d.offset = G_ADJ_STRIDE2, 2, -1, spec.pad
-    else:
+    if (spec.stride, spec.pad_mode) not in _DGRAD_GATHER:
         raise L.MCAVError("conv_dgrad: unsupported stride/padding combination")
-    d.pad_mode = PAD_ZERO
-    d.y, d.Hd, d.Wd, d.Cd, d.n_begin, d.n_count, d.y_choff = P(y), Hs, Ws, y.shape[3], n_begin, n_count, 0
-    d.bias, d.act = None, ACT_NONE
+    mode, stride, sign, offset = _DGRAD_GATHER[spec.stride, spec.pad_mode]
+    d = _igemm_desc(dy, None, (B, Hd, Wd, Cout, 0, 0), (spec.kh, spec.kw, up16(spec.cin), up16(spec.cout)),
+                    (mode, stride, sign, spec.pad if offset is None else offset, PAD_ZERO), y, (Hs, Ws, n_begin, n_count), tile)
     d.dact_aux, d.dact, d.addend, d.pool = P(dact_aux), dact, P(addend), int(pool)
-    d.tile = tile
     _weights_for(spec, d, True)
     slab = None
     if bn_stats is not None:
@@ -629,11 +684,14 @@ def conv_dgrad(spec, dy, in_shape, n_begin=0, n_count=None, out=None, dact_aux=N
             raise L.MCAVError("mcav_igemm_mtiles: invalid descriptor (%d)" % mt)
         slab = empty((mt, 2, n_count), dy)
         d.stats = P(slab)
-    with _Timed("dgrad", 2.0 * B * Hd * Wd * spec.cout * n_count * spec.kh * spec.kw,
+
+    def account():
+        return (2.0 * B * Hd * Wd * spec.cout * n_count * spec.kh * spec.kw,
                 "M=%d N=%d K=%dx%d s%d mode%d pool%d %dx%d%s%s" % (B * Hs * Ws, n_count, Cout, spec.kh * spec.kw, spec.stride, d.mode, int(pool), Hs, Ws,
                                                                   " +bn-bwd stats" if slab is not None else "", _pipe_tag(d)), None, _planes(d),
                 4.0 * (B * Hd * Wd * spec.cout + y.numel() * (1 + (dact_aux is not None) + (addend is not None) + (slab is not None))
-                       + spec.cout * n_count * spec.kh * spec.kw)):
+                       + spec.cout * n_count * spec.kh * spec.kw))
+    with _Timed("dgrad", account):
         _launch_igemm(d, "dgrad")
     return y if slab is None else (y, slab, slab.shape[0] // bn_stats[1].groups)
 
@@ -647,25 +705,15 @@ def _dgrad_upsample_merged(spec, dy, in_shape, c1, dact_aux, dact, addend, tile)
     B, Hd, Wd, Cout = dy.shape
     Hl, Wl = in_shape[0] // 2, in_shape[1] // 2
     tmp = empty((B, Hl + 2, Wl + 2, c1), dy)
-    d = IgemmDesc()
-    d.x1, d.x2 = P(dy), None
-    d.B, d.Hs, d.Ws, d.C1, d.C2, d.up1 = B, Hd, Wd, Cout, 0, 0
-    d.kh, d.kw, d.Np, d.Kp = 4, 4, up16(c1), up16(spec.cout)
-    d.mode, d.stride, d.sign, d.offset, d.pad_mode = G_DIRECT, 2, 1, -3, PAD_ZERO
-    d.y, d.Hd, d.Wd, d.Cd, d.n_begin, d.n_count, d.y_choff = P(tmp), Hl + 2, Wl + 2, c1, 0, c1, 0
-    d.bias, d.act = None, ACT_NONE
-    d.tile = tile & 0xff
-    d.w = P(spec.packed_upmerge_adj(c1))
-    if spec.mma in (MMA_BF16, MMA_SPLIT, MMA_SPLIT_ALL):
-        d.mma, d.w16 = spec.mma, d.w
-        if L.lib().mcav_igemm_uses_bf16(ctypes.byref(d)):
-            d.w16 = P(spec.packed_upmerge_adj(c1, bf16=3 if spec.mma >= MMA_SPLIT else True))
-        else:
-            d.mma, d.w16 = 0, None
-    with _Timed("dgrad", 2.0 * B * Hd * Wd * spec.cout * c1 * 9,
-                "M=%d N=%d K=%dx9 s1 mode2 pool1 (merged 4x4/s2) %dx%d" % (B * Hd * Wd, c1, Cout, Hd, Wd),
+    d = _igemm_desc(dy, None, (B, Hd, Wd, Cout, 0, 0), (4, 4, up16(c1), up16(spec.cout)), (G_DIRECT, 2, 1, -3, PAD_ZERO), tmp,
+                    (Hl + 2, Wl + 2, 0, c1), tile & TILE_ID_MASK)
+    _weights_for(spec, d, True, lambda: spec.packed_upmerge_adj(c1), lambda planes: spec.packed_upmerge_adj(c1, bf16=planes))
+
+    def account():
+        return (2.0 * B * Hd * Wd * spec.cout * c1 * 9, "M=%d N=%d K=%dx9 s1 mode2 pool1 (merged 4x4/s2) %dx%d" % (B * Hd * Wd, c1, Cout, Hd, Wd),
                 2.0 * B * (Hl + 2) * (Wl + 2) * spec.cout * c1 * 16, _planes(d),          # 16 taps per low-resolution pixel (incl. the ring) instead of 4 x 9
-                4.0 * (dy.numel() + B * Hl * Wl * c1 * (1 + (dact_aux is not None) + (addend is not None)) + spec.cout * c1 * 9)):
+                4.0 * (dy.numel() + B * Hl * Wl * c1 * (1 + (dact_aux is not None) + (addend is not None)) + spec.cout * c1 * 9))
+    with _Timed("dgrad", account):
         _launch_igemm(d, "dgrad, merged upsample")
         y = empty((B, Hl, Wl, c1), dy)
         L.check(L.lib().mcav_upsample_adj_fold(P(tmp), B, Hl, Wl, c1, P(dact_aux), dact, P(addend), P(y), L.stream()), "mcav_upsample_adj_fold")
@@ -680,33 +728,22 @@ class DyBn(_collections.namedtuple("DyBn", "x gamma mean invstd sums groups")):
     to it as it loads it (mcav_wgrad_desc.dy_bn_*).  x: the raw conv output; sums: [groups][2][C] of mcav_bn_bwd_finalize."""
 
 
+def _one_source(d, x, c, ci_offset, cin_total, up1, upm=0):
+    """Restricts a two-source WgradDesc to one of its sources: x alone ([.., c]), writing input channels [ci_offset, ci_offset + c) of the
+    gradient of a filter with cin_total input channels."""
+    d.x1, d.x2, d.C1, d.C2, d.up1, d.Kp = P(x), None, c, 0, up1, c
+    d.Cin, d.Cin_total, d.ci_offset, d.upm = c, cin_total, ci_offset, upm
+
+
 def conv_wgrad(spec, x1, dy, x2=None, up1=False, tile=0, dy_bn=None):
     """Accumulates d loss / d weight (OIHW) and d loss / d bias into the parameters' .grad buffers."""
-    planar = x1 if isinstance(x1, PlanarImages) else None
-    if planar is not None and not (spec.is_stem() and x2 is None and not up1 and not (tile >> 9) & 1):
-        x1, planar = planar.packed(), None
-    B = x1.shape[0]
-    Hs, Ws = (x1.shape[1] * 2, x1.shape[2] * 2) if up1 else (x1.shape[1], x1.shape[2])
-    gw = grad_buffer(spec.weight)
-    gb = grad_buffer(spec.bias) if spec.bias is not None else None
-    d = WgradDesc()
-    if planar is not None:
-        planar.fill(d)
-        LAUNCHES["wgrad_planar"] += 1
-    else:
-        d.x1 = P(x1)
-    d.x2 = P(x2)
-    d.B, d.Hs, d.Ws, d.C1, d.C2, d.up1 = B, Hs, Ws, x1.shape[3], (x2.shape[3] if x2 is not None else 0), int(up1)
-    d.kh, d.kw, d.Kp = spec.kh, spec.kw, spec.kp
-    d.mode = G_SMALLC if spec.smallc else G_DIRECT
-    d.stride, d.sign, d.offset, d.pad_mode = spec.stride, 1, -spec.pad, spec.pad_mode
-    d.dy, d.Hd, d.Wd, d.Cdy, d.dy_choff = P(dy), dy.shape[1], dy.shape[2], dy.shape[3], 0
-    d.Cout, d.Cin = spec.cout, spec.cin
-    d.dw_oihw, d.accumulate, d.dbias = P(gw), 1, P(gb)
-    d.tile = tile
+    x1, source = _gather_source(x1, x2, up1, spec.takes_stem(x2, up1, tile), "wgrad_planar")
+    B, Hs, Ws, c1, c2 = source[:5]
     # MMA_SPLIT: the library takes the split form where it is ahead (wgrad3x3_patch_kernel: single-source 3x3 stride-1 layers of 64-channel
     # multiples) and the fp32 MFMA kernels elsewhere; MCAV_SPLIT_WGRAD=1 = the split form on every launch the bf16 kernels cover
-    d.mma = MMA_SPLIT_ALL if (spec.mma == MMA_SPLIT and SPLIT_WGRAD) else (spec.mma if spec.mma in (MMA_BF16, MMA_SPLIT, MMA_SPLIT_ALL) else 0)
+    mma = MMA_SPLIT_ALL if (spec.mma == MMA_SPLIT and SPLIT_WGRAD) else (spec.mma if spec.mma in (MMA_BF16, MMA_SPLIT, MMA_SPLIT_ALL) else 0)
+    d = _wgrad_desc(x1, x2, source, (spec.kh, spec.kw, spec.kp), spec.fwd_gather(), dy, spec.cout, spec.cin, grad_buffer(spec.weight),
+                    grad_buffer(spec.bias) if spec.bias is not None else None, tile, mma)
     keep = ()
     if dy_bn is not None:
         if dy_bn.x.shape != dy.shape or x2 is not None or up1:
@@ -717,39 +754,30 @@ def conv_wgrad(spec, x1, dy, x2=None, up1=False, tile=0, dy_bn=None):
         keep = (dy_bn.x, dy_bn.gamma, dy_bn.mean, dy_bn.invstd, dy_bn.sums)
         LAUNCHES["wgrad_dy_bn"] += 1
     bf16 = bool(d.mma and L.lib().mcav_wgrad_uses_bf16(ctypes.byref(d)))
-    flops = 2.0 * B * dy.shape[1] * dy.shape[2] * spec.cout * spec.cin * spec.kh * spec.kw
-    tag = "pix=%d Cout=%d Ktot=%dx%d s%d" % (B * dy.shape[1] * dy.shape[2], spec.cout, spec.cin, spec.kh * spec.kw, spec.stride)
-    c1 = x1.shape[3]
-    if bf16 and x2 is not None and c1 % 16 == 0 and x2.shape[3] % 16 == 0:
-        # bf16: the two sources as two single-source launches (a two-source row tile would fetch both tensors for every tap: measured 4x slower);
-        # each writes its own input-channel range of the OIHW gradient.  The merged-tap form is not used: the bf16 kernels are memory-bound.
-        c2 = x2.shape[3]
-        d.x1, d.x2, d.C1, d.C2, d.up1, d.Kp = P(x2), None, c2, 0, 0, c2
-        d.Cin, d.Cin_total, d.ci_offset, d.upm = c2, spec.cin, c1, 0
-        launch_wgrad(d, (x2, dy), flops * c2 / spec.cin, tag + " [second source, bf16]")
-        d.x1, d.C1, d.up1, d.Kp = P(x1), c1, int(up1), c1
-        d.Cin, d.ci_offset, d.dbias = c1, 0, None
-        launch_wgrad(d, (x1, dy), flops * c1 / spec.cin, tag + " [first source, bf16]")
+
+    def account(note):
+        """-> (flops, tag) of the launch `d` describes at the time: the whole filter's, or the share of one source's channels"""
+        flops = 2.0 * B * dy.shape[1] * dy.shape[2] * spec.cout * spec.cin * spec.kh * spec.kw
+        tag = "pix=%d Cout=%d Ktot=%dx%d s%d" % (B * dy.shape[1] * dy.shape[2], spec.cout, spec.cin, spec.kh * spec.kw, spec.stride)
+        return flops * d.Cin / spec.cin if d.Cin_total else flops, tag + note
+    sources16 = x2 is not None and c1 % 16 == 0 and c2 % 16 == 0
+    # bf16: the two sources as two single-source launches (a two-source row tile would fetch both tensors for every tap: measured 4x slower);
+    # each writes its own input-channel range of the OIHW gradient.  The merged-tap form is not used: the bf16 kernels are memory-bound.
+    # fp32: the skip tensor's channels as an ordinary weight gradient, the upsampled map's in merged-tap form (mcav_conv.h)
+    merged = (not bf16 and sources16 and up1 and spec.kh == 3 and spec.kw == 3 and spec.stride == 1 and spec.pad == 1 and spec.pad_mode == PAD_REFLECT
+              and Hs % 2 == 0 and Ws % 2 == 0 and not tile & TILE_NO_UPMERGE
+              and (spec.cout >= 64 or bool(tile & TILE_ALT_UPMERGE)       # measured: 32 output channels are faster in one launch ...
+                   or (d.mma >= MMA_SPLIT and spec.cout == 32 and c2 % 64 == 0)))      # ... unless the skip half takes the patch kernel
+    if (bf16 and sources16) or merged:
+        _one_source(d, x2, c2, c1, spec.cin, 0)
+        _launch_wgrad(d, (x2, dy), lambda: account(" [skip half]" if merged else " [second source, bf16]"))
+        _one_source(d, x1, c1, 0, spec.cin, int(up1), upm=int(merged))
+        d.dbias = None                                   # (the first launch carried it)
+        if merged:
+            d.tile = 0
+        _launch_wgrad(d, (x1, dy), lambda: account(" [upsampled half, merged taps]" if merged else " [first source, bf16]"))
         return
-    if (not bf16 and up1 and x2 is not None and spec.kh == 3 and spec.kw == 3 and spec.stride == 1 and spec.pad == 1 and spec.pad_mode == PAD_REFLECT
-            and c1 % 16 == 0 and x2.shape[3] % 16 == 0 and Hs % 2 == 0 and Ws % 2 == 0 and not (tile >> 11) & 1
-            and (spec.cout >= 64 or (tile >> 12) & 1          # measured: 32 output channels are faster in one launch (bit 12 forces) ...
-                 or (d.mma >= MMA_SPLIT and spec.cout == 32 and x2.shape[3] % 64 == 0))):      # ... unless the skip half takes the patch kernel
-        # two launches: the skip tensor's channels as an ordinary weight gradient, the upsampled map's in merged-tap form (mcav_conv.h)
-        c2 = x2.shape[3]
-        d.x1, d.x2, d.C1, d.C2, d.up1, d.Kp = P(x2), None, c2, 0, 0, up16(c2)
-        d.Cin, d.Cin_total, d.ci_offset, d.upm = c2, spec.cin, c1, 0
-        launch_wgrad(d, (x2, dy), flops * c2 / spec.cin, tag + " [skip half]")
-        d.x1, d.C1, d.up1, d.Kp = P(x1), c1, 1, c1
-        d.Cin, d.ci_offset, d.upm, d.dbias, d.tile = c1, 0, 1, None, 0
-        launch_wgrad(d, (x1, dy), flops * c1 / spec.cin, tag + " [upsampled half, merged taps]", flops * c1 / spec.cin * 4.0 / 9.0)
-        return
-    executed = flops
-    if spec.is_stem() and x2 is None and not up1 and not (tile >> 9) & 1:
-        executed = flops * (8.0 / 7.0) * (1.0 if spec.cout >= 32 else 2.0)
-    elif up1 and x2 is None and spec.kh == 3 and spec.pad_mode == PAD_REFLECT and c1 == 16 and spec.cout <= 16 and not (tile >> 9) & 1:
-        executed = flops * 4.0 / 9.0                                      # level 0: conv3x3_halo_wgrad_up_kernel (merged taps)
-    launch_wgrad(d, (x1, x2, dy) + keep, flops, tag + (" [bn backward folded into dy]" if dy_bn is not None else ""), executed)
+    _launch_wgrad(d, (x1, x2, dy) + keep, lambda: account(" [bn backward folded into dy]" if dy_bn is not None else ""))
 
 
 class _WgradSide:
@@ -908,7 +936,7 @@ class _WgradBatch:
             table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
             hit = self.tables[key] = (table, pb.value, rb.value, lds.value)
         table, npb, nrb, nlds = hit
-        with _Timed("wgrad", 0.0, "slab reduction of %d weight gradients (batched)" % n):
+        with _Timed("wgrad", lambda: (0.0, "slab reduction of %d weight gradients (batched)" % n, None, 0, 0.0)):
             L.check(h.mcav_wgrad_reduce_multi(P(table), n, npb, nrb, nlds, L.stream()), "mcav_wgrad_reduce_multi")
 
 
@@ -919,9 +947,14 @@ LAST_WGRAD_PLANES = 0
 
 
 def launch_wgrad(d, tensors, flops=0.0, tag="", executed=None):
-    """mcav_wgrad for a filled descriptor (workspace handling + stream choice).  tensors: what the launch reads."""
+    """mcav_wgrad for a filled descriptor (workspace handling + stream choice).  tensors: what the launch reads.  executed None: what the
+    planned route does for `flops`."""
+    _launch_wgrad(d, tensors, lambda: (flops, tag), executed)
+
+
+def _launch_wgrad(d, tensors, account, executed=None):
+    """launch_wgrad with the accounting as a callable -> (flops, tag), asked only when PROFILE is a list."""
     h = L.lib()
-    abytes = 4.0 * (sum(t.numel() for t in tensors if t is not None) + d.Cout * d.Cin * d.kh * d.kw)
     nbytes = h.mcav_wgrad_workspace_bytes(ctypes.byref(d))
     if nbytes == 0:
         raise L.MCAVError("mcav_wgrad: invalid descriptor")
@@ -933,9 +966,16 @@ def launch_wgrad(d, tensors, flops=0.0, tag="", executed=None):
     planes = _planes(d) if (d.mma and h.mcav_wgrad_uses_bf16(ctypes.byref(d))) else 0
     global LAST_WGRAD_PLANES
     LAST_WGRAD_PLANES = planes                      # (tests: which pipe the last weight-gradient launch took -- 6: split form, 1: bf16, 0: fp32 MFMA)
-    if planes:
-        tag += _pipe_tag(d)
-    defer = WGRAD_BATCH.enabled and dev.type == "cuda" and WGRAD_SIDE._note(torch.cuda.current_stream())
+
+    def record():
+        flops, tag = account()
+        r = _planned(d)
+        done = executed
+        if done is None:                                 # 4 merged taps instead of 9 (the upsampled half of a two-launch gradient; level 0's halo kernel)
+            done = _stem_executed(flops, d.Cout) if r.family == WGRAD_STEM else flops * 4.0 / 9.0 if r.variant & RV_UPM else flops
+        return (flops, tag + (_pipe_tag(d) if planes else ""), done, planes,
+                4.0 * (sum(t.numel() for t in tensors if t is not None) + d.Cout * d.Cin * d.kh * d.kw))
+    defer =WGRAD_BATCH.enabled and dev.type == "cuda" and WGRAD_SIDE._note(torch.cuda.current_stream())
     if defer:
         # inside a backward pass: GEMM now, the slab reduction with its bucket (grads_ready / the end-of-backward join).  The descriptor is
         # copied: the caller re-uses `d` for its next launch.
@@ -948,7 +988,7 @@ def launch_wgrad(d, tensors, flops=0.0, tag="", executed=None):
         dd = WgradDesc.from_buffer_copy(d)
 
         def go_deferred():
-            with _Timed("wgrad", flops, tag, executed, planes, abytes):
+            with _Timed("wgrad", record):
                 L.check(h.mcav_wgrad_deferred(ctypes.byref(dd), P(ws), ws.numel(), ctypes.byref(item), L.stream()), "mcav_wgrad_deferred")
         WGRAD_SIDE.run(go_deferred, tensors)
         WGRAD_BATCH.items.append(item)
@@ -956,7 +996,7 @@ def launch_wgrad(d, tensors, flops=0.0, tag="", executed=None):
 
     def go():
         ws = L.workspace(nbytes, dev, "wgrad")
-        with _Timed("wgrad", flops, tag, executed, planes, abytes):
+        with _Timed("wgrad", record):
             L.check(h.mcav_wgrad(ctypes.byref(d), P(ws), ws.numel(), L.stream()), "mcav_wgrad")
     WGRAD_SIDE.run(go, tensors)
 
@@ -1206,7 +1246,7 @@ def narrow_ok(spec, x):
 def conv3x3r_c1_fwd(spec, x, act):
     B, H, W, C = x.shape
     y = empty((B, H, W, 1), x)
-    with _Timed("fwd", 2.0 * B * H * W * C * 9, "head M=%d N=1 K=%dx9 %dx%d" % (B * H * W, C, H, W), None, 0, 4.0 * (x.numel() + y.numel())):
+    with _Timed("fwd", lambda: (2.0 * B * H * W * C * 9, "head M=%d N=1 K=%dx9 %dx%d" % (B * H * W, C, H, W), None, 0, 4.0 * (x.numel() + y.numel()))):
         L.check(L.lib().mcav_conv3x3r_c1_fwd(P(x), B, H, W, C, P(spec.weight), P(spec.bias), act, P(y), L.stream()), "mcav_conv3x3r_c1_fwd")
     return y
 
@@ -1221,8 +1261,8 @@ def conv3x3r_c1_bwd(spec, x, dy, y, act, x_act, addend=None):
     dx = torch.empty_like(x)
     gw = grad_buffer(spec.weight)
     gb = grad_buffer(spec.bias) if spec.bias is not None else None
-    with _Timed("dgrad", 4.0 * B * H * W * C * 9, "head bwd (dgrad+wgrad) M=%d K=%dx9 %dx%d" % (B * H * W, C, H, W), None, 0,
-                4.0 * (2 * x.numel() + dy.numel() + (addend.numel() if addend is not None else 0))):
+    with _Timed("dgrad", lambda: (4.0 * B * H * W * C * 9, "head bwd (dgrad+wgrad) M=%d K=%dx9 %dx%d" % (B * H * W, C, H, W), None, 0,
+                                  4.0 * (2 * x.numel() + dy.numel() + (addend.numel() if addend is not None else 0)))):
         L.check(h.mcav_conv3x3r_c1_bwd(P(x), B, H, W, C, P(spec.weight), P(dy), P(y), act, x_act, P(addend), P(dx), P(gw), P(gb), 1,
                                        P(ws), ws.numel(), L.stream()), "mcav_conv3x3r_c1_bwd")
     return dx

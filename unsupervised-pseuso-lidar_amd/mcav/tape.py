@@ -89,13 +89,9 @@ def deconv(tape, ds, x, out_hw, act=N.ACT_RELU):
     H, W = out_hw
     spec = ds.as_conv                                   # cout(spec) = Cin of the deconv, cin(spec) = Cout of the deconv
     y = N.empty((B, H, W, ds.cout), x)
-    d = N.IgemmDesc()
-    d.x1, d.x2 = P(x), None
-    d.B, d.Hs, d.Ws, d.C1, d.C2, d.up1 = B, Hs, Ws, C, 0, 0
+    d = N._igemm_desc(x, None, (B, Hs, Ws, C, 0, 0), (3, 3, N.up16(ds.cout), N.up16(ds.cin)), (N.G_ADJ_STRIDE2, 2, -1, 1, N.PAD_ZERO), y,
+                      (H, W, 0, ds.cout))
     d.w = P(spec.packed_bwd())                          # [n = I (deconv Cout)][tap][k = O (deconv Cin)]
-    d.kh, d.kw, d.Np, d.Kp = 3, 3, N.up16(ds.cout), N.up16(ds.cin)
-    d.mode, d.stride, d.sign, d.offset, d.pad_mode = N.G_ADJ_STRIDE2, 2, -1, 1, N.PAD_ZERO
-    d.y, d.Hd, d.Wd, d.Cd, d.n_begin, d.n_count, d.y_choff = P(y), H, W, ds.cout, 0, ds.cout, 0
     d.bias, d.act = P(ds.bias), act
     L.check(L.lib().mcav_igemm(ctypes.byref(d), L.stream()), "mcav_igemm(deconv)")
 
@@ -105,15 +101,8 @@ def deconv(tape, ds, x, out_hw, act=N.ACT_RELU):
             return
         dpre = gy if act == N.ACT_NONE else N.act_bwd(gy, y, act)
         # weight gradient [Cin][Cout][3][3]: "source" = dpre gathered with stride 2, "dy" = x
-        gw = N.grad_buffer(ds.weight)
-        wd = N.WgradDesc()
-        wd.x1, wd.x2 = P(dpre), None
-        wd.B, wd.Hs, wd.Ws, wd.C1, wd.C2, wd.up1 = B, H, W, ds.cout, 0, 0
-        wd.kh, wd.kw, wd.Kp = 3, 3, N.up16(ds.cout)
-        wd.mode, wd.stride, wd.sign, wd.offset, wd.pad_mode = N.G_DIRECT, 2, 1, -1, N.PAD_ZERO
-        wd.dy, wd.Hd, wd.Wd, wd.Cdy, wd.dy_choff = P(x), Hs, Ws, C, 0
-        wd.Cout, wd.Cin = ds.cin, ds.cout
-        wd.dw_oihw, wd.accumulate, wd.dbias, wd.tile = P(gw), 1, None, 0
+        wd = N._wgrad_desc(dpre, None, (B, H, W, ds.cout, 0, 0), (3, 3, N.up16(ds.cout)), (N.G_DIRECT, 2, 1, -1, N.PAD_ZERO), x, ds.cin, ds.cout,
+                           N.grad_buffer(ds.weight), None)
         N.launch_wgrad(wd, (dpre, x))
         colsum(dpre, N.grad_buffer(ds.bias), accumulate=True)
         # data gradient: the ordinary stride-2 conv of dpre with the same weights (O = Cin)
