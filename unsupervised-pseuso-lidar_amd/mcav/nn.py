@@ -1258,7 +1258,7 @@ def conv3x3r_c1_bwd(spec, x, dy, y, act, x_act, addend=None):
     if act != ACT_NONE and B * H * W >= (1 << 16):      # large maps: one elementwise pass for dy * act'(y), then half the gathers
         dy, y, act = act_bwd(dy, y, act), None, ACT_NONE
     ws = L.workspace(h.mcav_conv3x3r_c1_bwd_workspace_bytes(C), x.device, "narrow")
-    dx = torch.empty_like(x)
+    dx = empty(x.shape, x)
     gw = grad_buffer(spec.weight)
     gb = grad_buffer(spec.bias) if spec.bias is not None else None
     with _Timed("dgrad", lambda: (4.0 * B * H * W * C * 9, "head bwd (dgrad+wgrad) M=%d K=%dx9 %dx%d" % (B * H * W, C, H, W), None, 0,
