@@ -499,6 +499,52 @@ int mcav_pillarize_indexed(const float* points, const int* offsets, int B, long 
 int mcav_pillarize_bwd(const float* d_voxels, const int* slot_points, const int* num_points, const int* pillar_offsets, int B,
                        long long capacity, int max_points, int flags, float* d_points, long long n_max, void* stream);
 
+/* Cloud batch -> soft-occupancy canvas, the input of a detector that reads a dense voxel grid (PIXOR): End-to-End Pseudo-LiDAR's
+ * differentiable quantisation.  The definition is tests/quant_ref.py; the arithmetic is csrc/quant_math.h.
+ *   input    points, offsets, B, n_max: as mcav_pillarize takes them; n = min(offsets[B], n_max), rows at and beyond n are never read.
+ *   grid     nx x ny x nz cells of vx x vy x vz from (x0, y0, z0)
+ *   cell     mcav_pillarize's rule on all three axes: fz = floorf((z - z0) / vz) as fx and fy, the point is kept iff 0 <= fx < nx,
+ *            0 <= fy < ny and 0 <= fz < nz, compared as floats (a NaN or an infinity drops the point); n(m') = the kept points of an
+ *            image in cell m'.
+ *   centre   cx = (float)ix * vx + (vx * 0.5f + x0), likewise cy, cz: float32, every operation rounded on its own
+ *   term     for a kept point p of cell m' and every cell m of the 3 x 3 x 3 block around m' inside the grid: dx = x - cx(m), dy, dz;
+ *            d2 = dx * dx, d2 = fmaf(dy, dy, d2), d2 = fmaf(dz, dz, d2); t = -(d2 / sigma2) (IEEE division); e = quant_exp(t), the
+ *            float32 exponential of csrc/quant_math.h (at most 0.9375 ulp from exp(t); +0 for t < -87)
+ *   sum      q = llrint((double)e * 2^40 / (double)(n(m') * (m == m' ? 1 : 26))); S(m) = the 64-bit integer sum of q over every term that
+ *            lands on m; canvas[b, iz, iy, ix] = (float)((double)S(m) * 2^-40): E2E-PL's T(m) = T(m, m) + 1/26 sum over the neighbours m'
+ *            of T(m, m'), T(m, m') the mean of e over the points of m'.  |N_m| is 26 everywhere: a neighbour outside the grid is empty.
+ *   canvas   device [B, nz, ny, nx] float32; one call writes every element: no zero-fill by the caller.
+ *   point_count  device int32 [n_max] or NULL: n(m') of every kept row below n, 0 for a dropped one; rows at and beyond n are not written.
+ * Integer atomics only and integer sums: no output depends on the order in which they land, any number of points may share a cell, two
+ * runs give the same bytes.  No host synchronisation, allocation or copy (one hipMemsetAsync of the column counters): the call can be
+ * captured.  7 launches (5 when n_max = 0): a counting sort of the rows by (b, iy, ix), then one workgroup per 4 x 64 columns of an image
+ * for the cell counts and for the canvas, whose tile of sums lives in LDS (512 nz bytes of it per column).
+ * Workspace (mcav_cloud_occupancy_workspace_bytes, 0 for sizes that are refused; scratch of one call, no zero-fill, each piece rounded up
+ * to 256 bytes): 4 (B ny nx + 1) + 4 ceil(B ny nx / 1024) + 16 n_max bytes.
+ * Returns MCAV_E_INVALID for a null points, offsets, canvas or workspace, B <= 0, B > 65535, n_max < 0, n_max >= 2^31, nx or ny < 1, nz
+ * outside [1, 64], B * nz * ny * nx >= 2^31, a vx, vy, vz or sigma2 that is not finite and positive, a non-finite x0, y0 or z0, a
+ * points, canvas or workspace address that is no multiple of 16, or an offsets or point_count address that is no multiple of 4;
+ * MCAV_E_WORKSPACE for a short workspace; nothing is launched then. */
+size_t mcav_cloud_occupancy_workspace_bytes(int B, long long n_max, int nz, int ny, int nx);
+int mcav_cloud_occupancy(const float* points, const int* offsets, int B, long long n_max, float x0, float y0, float z0, float vx, float vy,
+                         float vz, int nx, int ny, int nz, float sigma2, float* canvas, int* point_count /* may be null */,
+                         void* workspace, size_t workspace_bytes, void* stream);
+/* The backward of mcav_cloud_occupancy: the gradient of the canvas -> the gradient of the cloud rows.  The counts and the fixed-point
+ * rounding are piecewise constant: the derivative is that of the unrounded expression.  points, offsets, the grid and sigma2 are the
+ * forward's, point_count what it recorded; d_canvas: device [B, nz, ny, nx] float32; d_points: device [n_max, 4] float32, every row
+ * written.  A kept row i below n with count c = point_count[i], its cell recomputed from the point as in the forward:
+ *   d_points[i][0] = (float) sum over the cells m of the 3 x 3 x 3 block inside the grid, in ascending (dz, dy, dx) order from +0.0, of
+ *                    (((double)d_canvas[m] * (w / (double)c)) * (double)e) * ((-2.0 * (double)dx) / (double)sigma2)
+ *   with w = 1.0 for the point's own cell and 1.0 / 26.0 for a neighbour, e and dx the forward's float32 values, every operation float64
+ *   and rounded on its own; columns 1 and 2 likewise with dy and dz.  Column 3, every dropped row and every row at and beyond n: +0.0.
+ * A row has one destination: no atomics, the same bytes from run to run.  1 launch, one thread per row, no workspace, no host
+ * synchronisation: the call can be captured.
+ * Returns MCAV_E_INVALID for a null pointer, what the forward refuses of B, n_max, the grid and sigma2, a points or d_points address that
+ * is no multiple of 16 or an offsets, point_count or d_canvas address that is no multiple of 4; nothing is launched then. */
+int mcav_cloud_occupancy_bwd(const float* points, const int* offsets, const int* point_count, const float* d_canvas, int B, long long n_max,
+                             float x0, float y0, float z0, float vx, float vy, float vz, int nx, int ny, int nz, float sigma2,
+                             float* d_points, void* stream);
+
 /* Pillars -> pillar features -> bird's-eye-view pseudo-image, the first layers of a LiDAR 3-D detector (PointPillars / SECOND / OpenPCDet:
  * PillarVFE's Linear + BatchNorm1d + ReLU + max over the pillar's points with the BatchNorm folded into the layer, then
  * PointPillarScatter), in one launch.  The definition is tests/pfn_ref.py; the arithmetic is csrc/pfn_math.h.

@@ -135,6 +135,13 @@ class Inference:
         return pb
 
     @torch.no_grad()
+    def occupancy(self, samples, grid=None, sigma2=0.01, **cloud_kw):
+        """One batch of a datasets.calibration loader -> the soft-occupancy canvas [B, nz, ny, nx] of clouds(samples, **cloud_kw)
+        (pseudo_lidar.occupancy; default PIXOR's 700 x 800 x 35 grid).  Nothing is read back, and nothing is written to disk: a canvas
+        is 78 MB per frame."""
+        return self.clouds(samples, **cloud_kw).occupancy(grid=grid, sigma2=sigma2)
+
+    @torch.no_grad()
     def pseudo_images(self, samples, pfn, layout="nchw", **pillar_kw):
         """One batch of a datasets.calibration loader -> [B, C_out, ny, nx]: pillars(samples, **pillar_kw) through the PillarFeatureNet
         `pfn` into the bird's-eye-view pseudo-image (pseudo_lidar.PillarFeatureNet.pseudo_image).  Nothing is read back."""

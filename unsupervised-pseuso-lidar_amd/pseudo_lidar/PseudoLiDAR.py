@@ -16,8 +16,9 @@ import torch
 
 from mcav import lib as L
 
-from .clouds import (BeamTables, CloudBatch, GDCResult, GroundScale, PillarBatch, PillarGrid, beam_tables, gdc, grid_intrinsics,  # noqa: F401
-                     ground_scale, pillarize, pillarize_backward, project_batch, project_batch_backward)
+from .clouds import (BeamTables, CloudBatch, GDCResult, GroundScale, OccupancyBatch, PillarBatch, PillarGrid, VoxelGrid,  # noqa: F401
+                     beam_tables, gdc, grid_intrinsics, ground_scale, occupancy, occupancy_backward, pillarize, pillarize_backward,
+                     project_batch, project_batch_backward)
 
 L.register({
     "mcav_pseudo_lidar_workspace_bytes": (L.c_sz, [L.c_i, L.c_i]),

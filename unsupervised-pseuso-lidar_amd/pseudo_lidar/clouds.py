@@ -14,6 +14,10 @@ corrected map goes into project_batch(input="depth").
 `pillarize(points, offsets)` / `CloudBatch.pillars()` turn a cloud batch into what a LiDAR 3-D detector reads (PointPillars / SECOND /
 OpenPCDet): a `PillarBatch` of voxels [P, N, C], coords [P, 4] and num_points [P] on a `PillarGrid`, the first N points of every non-empty
 cell in cloud order (mcav_pillarize; the definition is tests/pillar_ref.py); `PillarBatch.pseudo_image(net)`: PillarFeatureNet.py.
+`occupancy(points, offsets)` / `CloudBatch.occupancy()` is the other change of representation End-to-End Pseudo-LiDAR defines, the soft
+quantisation for detectors that read a dense voxel grid (PIXOR): a [B, nz, ny, nx] canvas on a `VoxelGrid` in which every cell holds
+the mean Gaussian weight of its own points plus 1/26 of its 26 neighbours' (mcav_cloud_occupancy; the definition is tests/quant_ref.py),
+differentiable back to the cloud rows (mcav_cloud_occupancy_bwd) and from there, through project_batch, to the disparity.
 """
 import ctypes
 
@@ -48,6 +52,10 @@ L.register({
     "mcav_pillarize_indexed": (L.c_i, [L.c_p, L.c_p, L.c_i, ctypes.c_longlong] + [L.c_f] * 6 + [L.c_i] * 4 + [L.c_p] * 3 +
                                [ctypes.c_longlong, L.c_p, L.c_p, L.c_p, L.c_sz, L.c_p]),
     "mcav_pillarize_bwd": (L.c_i, [L.c_p] * 4 + [L.c_i, ctypes.c_longlong, L.c_i, L.c_i, L.c_p, ctypes.c_longlong, L.c_p]),
+    "mcav_cloud_occupancy_workspace_bytes": (L.c_sz, [L.c_i, ctypes.c_longlong, L.c_i, L.c_i, L.c_i]),
+    "mcav_cloud_occupancy": (L.c_i, [L.c_p, L.c_p, L.c_i, ctypes.c_longlong] + [L.c_f] * 6 + [L.c_i] * 3 + [L.c_f, L.c_p, L.c_p, L.c_p, L.c_sz,
+                                     L.c_p]),
+    "mcav_cloud_occupancy_bwd": (L.c_i, [L.c_p] * 4 + [L.c_i, ctypes.c_longlong] + [L.c_f] * 6 + [L.c_i] * 3 + [L.c_f, L.c_p, L.c_p]),
 })
 
 PLB_INPUT_DEPTH = GS_INPUT_DEPTH = PILLAR_DECORATE = 1         # include/mcav_depth.h MCAV_PLB_INPUT_DEPTH, MCAV_GS_INPUT_DEPTH, MCAV_PILLAR_DECORATE
@@ -253,6 +261,10 @@ class CloudBatch(OffsetBatch):
     def pillars(self, **kw):
         """pillarize(self.points, self.offsets, **kw) -> PillarBatch (grid, max_points, capacity, decorate, out, provenance)"""
         return pillarize(self.points, self.offsets, **kw)
+
+    def occupancy(self, **kw):
+        """occupancy(self.points, self.offsets, **kw) -> the [B, nz, ny, nx] canvas (grid, sigma2, out, provenance)"""
+        return occupancy(self.points, self.offsets, **kw)
 
 
 def project_batch(m, P, T, sparsity, sizes=None, input="disparity", scale=1.0, intensity=None, max_height=1.0, max_depth=None, beams=None,
@@ -578,4 +590,132 @@ def _pillarize_backward(f, grad_voxels, out):
     with torch.cuda.device(dev):
         L.check(L.lib().mcav_pillarize_bwd(L.ptr(grad_voxels), L.ptr(f["slot_points"]), L.ptr(f["num_points"]), L.ptr(f["offsets"]), B, cap, N,
                                            PILLAR_DECORATE if C == 9 else 0, L.ptr(out), n_max, L.stream()), "mcav_pillarize_bwd")
+    return out
+
+
+class VoxelGrid:
+    """The cells of occupancy: ranges x, y, z in metres (velodyne frame) and the cell's size (vx, vy, vz).  nx = round((x1 - x0) / vx), ny
+    and nz likewise; nz, the canvas' channels, lies in 1..64.  The default is PIXOR's grid: 700 x 800 x 35 cells of 0.1 m.  Empty,
+    reversed or non-finite ranges and sizes are refused.  The kernels take the scalars as float32."""
+
+    def __init__(self, x=(0.0, 70.0), y=(-40.0, 40.0), z=(-2.5, 1.0), size=(0.1, 0.1, 0.1)):
+        try:
+            vals = [float(v) for group in (x, y, z, size) for v in group]
+            if [len(group) for group in (x, y, z, size)] != [2, 2, 2, 3]:
+                raise ValueError
+        except (TypeError, ValueError):
+            raise L.MCAVError("VoxelGrid: x, y, z are (low, high) pairs and size is (vx, vy, vz), got %r %r %r %r" % (x, y, z, size))
+        with np.errstate(over="ignore"):
+            f32 = np.array(vals, np.float64).astype(np.float32)
+        if not np.isfinite(f32).all():
+            raise L.MCAVError("VoxelGrid: every range and size must be finite (in float32), got %r" % (vals,))
+        self.x, self.y, self.z, self.size = tuple(vals[0:2]), tuple(vals[2:4]), tuple(vals[4:6]), tuple(vals[6:9])
+        if not (f32[6:] > 0).all():
+            raise L.MCAVError("VoxelGrid: the cell size must be positive, got %r" % (self.size,))
+        if not (f32[1] > f32[0] and f32[3] > f32[2] and f32[5] > f32[4]):
+            raise L.MCAVError("VoxelGrid: empty range in x %r, y %r or z %r" % (self.x, self.y, self.z))
+        self.nx, self.ny, self.nz = (int(round((r[1] - r[0]) / s)) for r, s in zip((self.x, self.y, self.z), self.size))
+        if self.nx < 1 or self.ny < 1 or not 1 <= self.nz <= 64 or self.nx * self.ny * self.nz >= 2 ** 31:
+            raise L.MCAVError("VoxelGrid: %d x %d x %d cells (nz must be in 1..64, fewer than 2^31 in all)" % (self.nx, self.ny, self.nz))
+
+    def scalars(self):
+        """x0, y0, z0, vx, vy, vz, nx, ny, nz as the C calls take them"""
+        return self.x[0], self.y[0], self.z[0], self.size[0], self.size[1], self.size[2], self.nx, self.ny, self.nz
+
+    def __repr__(self):
+        return "VoxelGrid(x=%r, y=%r, z=%r, size=%r) [%d x %d x %d]" % (self.x, self.y, self.z, self.size, self.nx, self.ny, self.nz)
+
+
+class OccupancyBatch:
+    """What occupancy fills and keeps, on the device: `canvas` [B, nz, ny, nx] float32, `point_count` int32 [n_max] with provenance (the
+    points that share each kept row's cell, 0 for a dropped row), the grid and sigma2 of the last call, and the call's workspace."""
+
+    def __init__(self, batch, grid, device):
+        self.canvas = torch.empty((int(batch), grid.nz, grid.ny, grid.nx), dtype=torch.float32, device=device)
+        self.grid, self.sigma2, self.point_count, self._ws = grid, None, None, None
+        self._fwd, self._stamp = None, 0                                # what occupancy_backward reads; calls so far
+
+
+def occupancy(points, offsets, grid=None, sigma2=0.01, out=None, provenance=False):
+    """A cloud batch -> its soft-occupancy canvas [B, nz, ny, nx] float32 (mcav_cloud_occupancy), z bins as channels.  points: [n_max, 4]
+    float32 (x, y, z, i) and offsets: int32 [B + 1] on the GPU, as a CloudBatch holds them (rows at and beyond offsets[B] are never
+    read).  grid: a VoxelGrid (default: PIXOR's 700 x 800 x 35 cells of 0.1 m).  canvas[b, iz, iy, ix] = the mean over the cell's points of
+    exp(-|p - c|^2 / sigma2), c the cell's centre, plus 1/26 of the same mean of each of its 26 neighbours' points against c; sums are
+    64-bit integers of 2^-40, so the canvas does not depend on the order of the rows.  sigma2: the squared width in m^2 (default 0.01).
+    Every element is written; no host synchronisation.  out: an OccupancyBatch to reuse with its workspace (needed under graph capture);
+    the return value is its `canvas`.
+    provenance: also fill out.point_count, int32 [n_max] (the canvas is the same, bit for bit); occupancy_backward then works on `out`.
+    Differentiable: with grad mode on and points that require a gradient (a differentiable project_batch's) the call is a node of the
+    autograd graph whose backward is occupancy_backward (mcav_cloud_occupancy_bwd): columns x, y, z of the rows get a gradient, the counts
+    and the fixed-point rounding are piecewise constant.  The OccupancyBatch must not be filled again before backward runs."""
+    if not torch.is_tensor(points) or not torch.is_tensor(offsets):
+        raise L.MCAVError("occupancy: points and offsets must be tensors on the GPU")
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise L.MCAVError("occupancy: points must be [n, 4] (x, y, z, i), got %s" % (tuple(points.shape),))
+    if offsets.dim() != 1 or offsets.numel() < 2:
+        raise L.MCAVError("occupancy: offsets must be [B + 1], got %s" % (tuple(offsets.shape),))
+    grid = VoxelGrid() if grid is None else grid
+    if not isinstance(grid, VoxelGrid):
+        raise L.MCAVError("occupancy: grid must be a VoxelGrid, got %r" % (grid,))
+    sigma2 = float(sigma2)
+    if not (np.isfinite(np.float32(sigma2)) and np.float32(sigma2) > 0):
+        raise L.MCAVError("occupancy: sigma2 must be finite and positive (in float32), got %r" % (sigma2,))
+    points, offsets = L.dev(points, "points"), L.dev(offsets, "offsets", torch.int32)
+    n_max, B, dev = points.shape[0], offsets.numel() - 1, points.device
+    if n_max == 0:
+        raise L.MCAVError("occupancy: points holds no rows")
+    shape = (B, grid.nz, grid.ny, grid.nx)
+    if out is None:
+        out = OccupancyBatch(B, grid, dev)
+    elif not isinstance(out, OccupancyBatch) or tuple(out.canvas.shape) != shape or L.dev(out.canvas, "out.canvas").device != dev:
+        raise L.MCAVError("occupancy: out must be an OccupancyBatch with a %s canvas on %s" % (list(shape), dev))
+    hl = L.lib()
+    nbytes = hl.mcav_cloud_occupancy_workspace_bytes(B, n_max, grid.nz, grid.ny, grid.nx)
+    if nbytes == 0:
+        raise L.MCAVError("occupancy: %d images of %d x %d x %d cells with %d rows are refused (B <= 65535, fewer than 2^31 cells and rows)"
+                          % (B, grid.nz, grid.ny, grid.nx, n_max))
+    out.grid, out.sigma2 = grid, sigma2
+    ws = out._ws = grown(out._ws, nbytes, dev)
+
+    def run(count):
+        with torch.cuda.device(dev):
+            L.check(hl.mcav_cloud_occupancy(L.ptr(points), L.ptr(offsets), B, n_max, *grid.scalars(), sigma2, L.ptr(out.canvas), L.ptr(count),
+                                            L.ptr(ws), ws.numel(), L.stream()), "mcav_cloud_occupancy")
+
+    out.canvas, out.point_count = recorded(
+        points, out, out.canvas, out.point_count, index_shape=(n_max,), provenance=provenance, run=run, saved=(points, offsets),
+        record=lambda count: dict(points=points.detach(), offsets=offsets, point_count=count, grid=grid, sigma2=sigma2, shape=shape, n_max=n_max),
+        backward=_occupancy_backward, again="backward: the OccupancyBatch was filled again after this forward")
+    return out.canvas
+
+
+def occupancy_backward(record, grad_canvas, out=None):
+    """The backward of occupancy as a plain call (mcav_cloud_occupancy_bwd; one launch, no host synchronisation).  record: an
+    OccupancyBatch filled by occupancy with provenance=True (or by a differentiable call), or its record `._fwd`; the points, offsets and
+    point_count still hold what they held.  grad_canvas: [B, nz, ny, nx] float32.  -> d_points [n_max, 4] float32, every row written:
+    columns x, y, z of a kept row get the float64 sum of its 27 terms' derivatives, rounded once; column 3, dropped rows and rows behind
+    the count get +0.0.  out: a tensor to fill (else a new one)."""
+    if isinstance(record, OccupancyBatch):
+        record = record._fwd
+        if record is None:
+            raise L.MCAVError("occupancy_backward: the OccupancyBatch holds no provenance (occupancy(..., provenance=True) records it)")
+    if not isinstance(record, dict) or record.get("point_count") is None:
+        raise L.MCAVError("occupancy_backward: record must be an OccupancyBatch or its record, got %r" % type(record).__name__)
+    return _occupancy_backward(record, grad_canvas, out)
+
+
+def _occupancy_backward(f, grad_canvas, out):
+    points, grid, n_max, shape = f["points"], f["grid"], f["n_max"], f["shape"]
+    dev = points.device
+    if not torch.is_tensor(grad_canvas) or tuple(grad_canvas.shape) != shape:
+        raise L.MCAVError("occupancy_backward: grad_canvas must be %s" % (list(shape),))
+    if L.dev(grad_canvas, "grad_canvas").device != dev:
+        raise L.MCAVError("occupancy_backward: grad_canvas is on %s, the cloud on %s" % (grad_canvas.device, dev))
+    if out is None:
+        out = torch.empty((n_max, 4), dtype=torch.float32, device=dev)
+    elif not torch.is_tensor(out) or tuple(out.shape) != (n_max, 4) or L.dev(out, "out").device != dev:
+        raise L.MCAVError("occupancy_backward: out must be float32 %s on %s" % ([n_max, 4], dev))
+    with torch.cuda.device(dev):
+        L.check(L.lib().mcav_cloud_occupancy_bwd(L.ptr(points), L.ptr(f["offsets"]), L.ptr(f["point_count"]), L.ptr(grad_canvas), shape[0], n_max,
+                                                 *grid.scalars(), f["sigma2"], L.ptr(out), L.stream()), "mcav_cloud_occupancy_bwd")
     return out
