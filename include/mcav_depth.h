@@ -771,6 +771,51 @@ int mcav_image_preprocess_augment(const unsigned char* src_bhwc, int B, int H0, 
                                   const mcav_augment_record* records, float* plain_bchw, float* aug_bchw, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* Oriented 3-D boxes: overlap and batched greedy non-maximum suppression, what follows a detector's head (OpenPCDet / second.pytorch
+ * iou3d_nms: boxes_iou_bev, boxes_iou3d, nms_gpu).  The definition is tests/box_ref.py; the arithmetic is csrc/box_math.h.
+ *   box      7 float32 (x, y, z, dx, dy, dz, heading): the centre, dx along the heading, the heading a rotation about +z, counter-
+ *            clockwise (OpenPCDet's LiDAR frame).  VALID when all seven are finite, 0.001 <= dx, dy, dz <= 1024 and |heading| <= 32
+ *            (above 8 pi).  An invalid box has overlap +0.0 with every box, itself included, and is never a candidate.
+ *   sincos   box_sincos of csrc/box_math.h: fmaf steps alone, the same bits on the host and the device, at most 1.5625 ulp from the
+ *            float64 sine and cosine over every allowed heading
+ *   inter    B's centre minus A's first; corners from (cos, sin, half extents); A's quadrilateral clipped against B's four half-planes
+ *            in a fixed order (Sutherland-Hodgman; inside is side >= 0 of a fixed fmaf expression, a crossing is strictly opposite
+ *            signs, at t = sp / (sp - sq)); at most 8 vertices; half the shoelace sum in a fixed order, clamped to [0, min(area A,
+ *            area B)].  +0.0 at once when the centres are further apart than the half-diagonals reach.  No epsilon constants.
+ *   iou      bev: inter / (area A + area B - inter); 3d: i3 / (vol A + vol B - i3), i3 = min(inter * max(0, min(top) - max(bottom)), vol A, vol B), the
+ *            box spanning z -+ dz / 2.  IEEE division; never above 1.
+ * mcav_box_iou: a [na, 7], b [nb, 7] -> out [na, nb] float32 on the device, out[i][j] = iou(a[i], b[j]) in `mode`, every element written.
+ * 1 launch (none when na or nb is 0), no workspace, no atomics, no host synchronisation.  Returns MCAV_E_INVALID for a null pointer, an
+ * address that is no multiple of 4, a negative na or nb or one above 65535 * 64, or an unknown mode; nothing is launched then. */
+#define MCAV_BOX_IOU_BEV 0
+#define MCAV_BOX_IOU_3D 1
+#define MCAV_NMS_MAX_CANDIDATES 4096
+int mcav_box_iou(const float* a, long long na, const float* b, long long nb, int mode, float* out, void* stream);
+/* mcav_box_nms: score threshold -> top pre_max -> greedy suppression, per image, over dense device inputs boxes [B, A, 7] float32,
+ * scores [B, A] float32 and classes [B, A] int32 (or NULL: one class).
+ *   1. Row i of an image is a candidate when its box is valid and score >= score_thresh (a NaN score never is; -0.0 counts as +0.0).
+ *   2. The candidates are ordered by score descending, then index ascending; beyond pre_max of them the first pre_max remain.
+ *   3. They are walked in that order; one is kept iff no earlier KEPT candidate of the same class has iou > iou_thresh with it
+ *      (iou(earlier, later) in `mode`); the walk stops after post_max kept.
+ *   4. keep [B, post_max] int32: the kept rows' indices in the order kept, -1 behind the count; num [B] int32: the count;
+ *      out_boxes [B, post_max, 7] and out_scores [B, post_max] (each may be NULL): the kept rows as they stand in the inputs, +0.0
+ *      behind the count.  One call writes every element of all four.
+ * Nothing returns to the host, no allocation, no global atomics (LDS integer counts in the radix select, exact in any order), nothing
+ * depends on timing: the call can be captured and two runs give the same bytes.  3 launches: select (one workgroup per image: count,
+ * radix select of the cut above pre_max, compaction in index order, an ordering of <= 4096 (key, index) pairs in LDS), mask (64 x 64 tiles
+ * of the upper triangle below the candidate count, a row's word is one 64-bit ballot), scan (one wavefront per image, 64 candidates
+ * at a time).
+ * Workspace (mcav_box_nms_workspace_bytes, 0 for sizes that are refused; scratch of one call, no zero-fill, each piece rounded up to
+ * 256 bytes): 4 B + B pre_max (4 + 4 + 80 + 8 ceil(pre_max / 64)) bytes.
+ * Returns MCAV_E_INVALID for a null boxes, scores, keep, num or workspace, B outside [1, 65535], A < 1, B * A >= 2^31, pre_max outside
+ * [1, MCAV_NMS_MAX_CANDIDATES], post_max outside [1, pre_max], a NaN threshold, an unknown mode, an address that is no multiple of 4 or
+ * a workspace address that is no multiple of 16; MCAV_E_WORKSPACE for a short workspace; nothing is launched and no output is touched
+ * then. */
+size_t mcav_box_nms_workspace_bytes(int B, long long A, int pre_max);
+int mcav_box_nms(const float* boxes, const float* scores, const int* classes /* may be null */, int B, long long A, float score_thresh,
+                 float iou_thresh, int mode, int pre_max, int post_max, int* keep, int* num, float* out_boxes /* may be null */,
+                 float* out_scores /* may be null */, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

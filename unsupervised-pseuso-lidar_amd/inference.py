@@ -5,6 +5,7 @@
     cb = inf.clouds(samples, beams=beam_tables())      # a pseudo_lidar.CloudBatch for one loader batch
     pb = inf.pillars(samples, max_points=32)           # a pseudo_lidar.PillarBatch: what a LiDAR 3-D detector reads
     img = inf.pseudo_images(samples, pfn)              # [B, C_out, ny, nx]: what the detector's convolutional backbone reads
+    det = inf.detections(samples, pfn, head)           # a pseudo_lidar.DetectionBatch: head(img) -> (boxes, scores) -> rotated NMS
     n = inf.export("out")                              # out/<date>/<drive>/pseudo_velodyne/data/<frame>.bin for every frame of the split
 
     python inference.py --config C --checkpoint X --out DIR [--beams NB NA] [--scale S | --scale ground] [--max-depth D]
@@ -38,7 +39,7 @@ import numpy as np
 import torch
 import yaml
 
-from pseudo_lidar import PillarFeatureNet, PillarGrid, PseudoLiDAR, beam_tables, gdc as gdc_correct, ground_scale
+from pseudo_lidar import PillarFeatureNet, PillarGrid, PseudoLiDAR, beam_tables, gdc as gdc_correct, ground_scale, nms as box_nms
 
 
 class Inference:
@@ -146,6 +147,15 @@ class Inference:
         """One batch of a datasets.calibration loader -> [B, C_out, ny, nx]: pillars(samples, **pillar_kw) through the PillarFeatureNet
         `pfn` into the bird's-eye-view pseudo-image (pseudo_lidar.PillarFeatureNet.pseudo_image).  Nothing is read back."""
         return pfn.pseudo_image(self.pillars(samples, **pillar_kw), layout=layout)
+
+    @torch.no_grad()
+    def detections(self, samples, net, head, pillar_kw=None, **nms_kw):
+        """One batch of a datasets.calibration loader -> DetectionBatch: pseudo_images(samples, net, **pillar_kw) -> head(canvas) ->
+        pseudo_lidar.nms(boxes, scores, **nms_kw).  net: the PillarFeatureNet; head: the caller's backbone and detection head, a callable
+        that takes the canvas [B, C_out, ny, nx] and returns (boxes [B, A, 7], scores [B, A] or [B, A, K]) on the GPU, decoded.  Nothing
+        is read back."""
+        boxes, scores = head(self.pseudo_images(samples, net, **dict(pillar_kw or {})))
+        return box_nms(boxes, scores, **nms_kw)
 
     def loader(self):
         """Every frame of the split, in order, with its calibration"""

@@ -3,3 +3,4 @@ from .PseudoLiDAR import (BeamTables, CloudBatch, GDCResult, GroundScale, Occupa
                           project_batch_backward)
 from .PillarFeatureNet import (PillarFeatureLayer, PillarFeatureNet, fold_batch, pillar_moments,  # noqa: F401
                                pillar_moments_backward)
+from .boxes import DetectionBatch, boxes_iou3d, boxes_iou_bev, nms  # noqa: F401
